@@ -13,6 +13,8 @@ Launch (driver contract):
   python bench.py --gpus N --steps K --warmup W
   # N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
   #        --master-addr 127.0.0.1 bench.py --gpus N ...
+  # --dump-outputs DIR  write the last timed step's outputs as DIR/*.npy
+  # --full              everything beyond the headline figure (nothing yet)
 
 Reference speed anchor: GNN train step ≈ 0.25 s/instance
 (unknown hardware) ⇒ 4 episodes/sec.
@@ -41,6 +43,43 @@ def build_cases(n_nodes, batch, distinct, T, seed, gtype="ba", workers=None):
         workers = max(2, 16 // max(world, 1))
     return build_training_cases(n_nodes, batch, distinct, T, seed,
                                 gtype=gtype, workers=workers)
+
+
+def dump_outputs(path, results, model):
+    """Write what the last timed step handed back as ``path/<name>.npy``:
+    the per-engine EpisodeResult fields and the model parameters after the
+    optimizer update (one flat vector, in ``model.parameters()`` order).
+    Floating arrays keep their dtype (fp32 on GPU, fp64 on CPU), counts are
+    stored as float64.  ``delay_emp`` is nan-padded past each graph's job
+    count; the padding is written as 0 so the files compare with plain
+    ``allclose`` (``num_jobs`` gives the valid prefix of every row)."""
+    import numpy as np
+
+    def host(t):
+        a = t.detach().cpu().numpy()
+        return a if a.dtype in (np.float32, np.float64) \
+            else a.astype(np.float64)
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for i, res in enumerate(results):
+        tag = "" if len(results) == 1 else f"_engine{i}"
+        valid = torch.arange(res.delay_emp.shape[1],
+                             device=res.delay_emp.device)[None, :] \
+            < res.num_jobs[:, None]
+        arrays["tau" + tag] = host(res.tau)
+        arrays["congest" + tag] = host(res.congest)
+        arrays["num_jobs" + tag] = host(res.num_jobs)
+        arrays["delay_emp" + tag] = host(torch.where(
+            valid, res.delay_emp, torch.zeros_like(res.delay_emp)))
+        arrays["loss_fn" + tag] = host(res.loss_fn).reshape(1)
+        arrays["loss_mse" + tag] = host(res.loss_mse).reshape(1)
+    arrays["params"] = host(torch.cat(
+        [p.detach().reshape(-1) for p in model.parameters()]))
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 * 2 ** 20, f"dump too large: {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main():
@@ -81,6 +120,16 @@ def main():
     ap.add_argument("--capture", action="store_true",
                     help="capture the whole training step in a hipGraph "
                          "and replay it (single-GPU)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed "
+                         "step computed (episode results + updated "
+                         "parameters) as DIR/<name>.npy; inputs are seeded, "
+                         "so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks beyond the "
+                         "headline figure (none at present: a plain run "
+                         "already does only set-up, warm-up and the timed "
+                         "steps)")
     args = ap.parse_args()
 
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -161,10 +210,11 @@ def main():
         else:
             for p in model.parameters():
                 p.grad = None
-        res = None
+        res = []                       # one EpisodeResult per engine
         for eng in engines:
             jobs = eng.sample_jobs(args.load, gen)
-            res = eng.gnn_episode(jobs, explore=0.0, gen=gen, train=True)
+            res.append(eng.gnn_episode(jobs, explore=0.0, gen=gen,
+                                       train=True))
         if use_fused:
             # one fused kernel: grad mean-scale, per-tensor clipnorm, Adam,
             # max_norm constraints; flat_g is the single RCCL payload
@@ -245,10 +295,12 @@ def main():
                 "load": args.load,
                 "T": args.T,
                 "parallelism": f"dp{n_gpus}",
-                "tau_gnn": float(torch.nanmean(last.tau)),
-                "congest_jobs": int(last.congest.sum()),
+                "tau_gnn": float(torch.nanmean(last[-1].tau)),
+                "congest_jobs": int(last[-1].congest.sum()),
             },
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last, model)
         print(json.dumps(out))
     if distributed:
         dist.destroy_process_group()
