@@ -21,8 +21,24 @@ def cheb_compat(model) -> bool:
 
 
 def cheb_lds_fits(Ee: int, K: int = 2) -> bool:
-    rows_pad = (Ee + 15) & ~15
-    return (3 * rows_pad * 33 + K * 32 * 32 + 32) * 4 <= 160 * 1024
+    """True when the LDS-resident kernels of this K hold a graph of Ee
+    extended links; decided by the extension from the same LDS plan that
+    sizes the launches."""
+    return dispatch.require_hip().cheb_fits_lds(Ee, K)
+
+
+def pack_cheb_params(params):
+    """Zero-pad the per-layer (weight (K,fi,fo), bias (fo)) sequence into
+    the (L,K,32,32) / (L,32) layout the fused kernels read."""
+    L = len(params) // 2
+    K = params[0].shape[0]
+    Wp = params[0].new_zeros(L, K, 32, 32)
+    bp = params[0].new_zeros(L, 32)
+    for l in range(L):
+        w, b = params[2 * l], params[2 * l + 1]
+        Wp[l, :w.shape[0], :w.shape[1], :w.shape[2]] = w
+        bp[l, :b.shape[0]] = b
+    return Wp, bp
 
 
 class ChebStackFn(torch.autograd.Function):
@@ -34,14 +50,8 @@ class ChebStackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, eng, *params):
         ext = dispatch.require_hip()
-        L = len(params) // 2
         K = params[0].shape[0]
-        Wp = x.new_zeros(L, K, 32, 32)
-        bp = x.new_zeros(L, 32)
-        for l in range(L):
-            w, b = params[2 * l], params[2 * l + 1]
-            Wp[l, :w.shape[0], :w.shape[1], :w.shape[2]] = w
-            bp[l, :b.shape[0]] = b
+        Wp, bp = pack_cheb_params(params)
         ctx.K = K
         ctx.large = not cheb_lds_fits(eng.Ee, K)
         if K > 2:

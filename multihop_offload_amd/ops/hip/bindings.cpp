@@ -59,6 +59,7 @@ std::vector<torch::Tensor> cheb_kn_bwd_hip(
     torch::Tensor dlam, torch::Tensor acts, torch::Tensor tks,
     torch::Tensor W, torch::Tensor ext_indptr, torch::Tensor ext_base,
     torch::Tensor ext_cols, long max_nnz);
+bool cheb_fits_lds(long Ee, long K);
 
 std::vector<torch::Tensor> cheb_large_fwd_hip(
     torch::Tensor x, torch::Tensor W, torch::Tensor bias,
@@ -85,6 +86,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("cheb_bwd_ablate", &cheb_bwd_hip_mask);
     m.def("cheb_kn_fwd", &cheb_kn_fwd_hip);
     m.def("cheb_kn_bwd", &cheb_kn_bwd_hip);
+    m.def("cheb_fits_lds", &cheb_fits_lds);
     m.def("fused_adam", &fused_adam_hip);
     m.def("cheb_large_fwd", &cheb_large_fwd_hip);
     m.def("cheb_large_bwd", &cheb_large_bwd_hip);

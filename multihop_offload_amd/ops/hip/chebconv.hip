@@ -20,79 +20,20 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include "cheb_tiles.h"
+
 namespace {
 
-#define DEV_INLINE __device__ __forceinline__
+using namespace cheb;
 
-constexpr int F = 32;          // padded feature width
-constexpr int STRIDE = 33;     // LDS row stride (f32) — breaks bank conflicts
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// row buffers (rows_pad×STRIDE each) in dynamic LDS; the launchers and
+// cheb_fits_lds size the launch from these
+constexpr int FWD_NBUF = 2;      // cheb_fwd_kernel: Xb | Tb
+constexpr int BWD_NBUF = 3;      // cheb_bwd_kernel: Ab | Db | Tb
+constexpr int KN_NBUF = 3;       // cheb_kn_*: Xb | Tb | Yb, Db | Pb | Qb
 
-// ---- dense tile product: dst(+)= src · W  (or · Wᵀ), MFMA 16×16×4 --------
-// src: LDS [rows_pad][STRIDE]; W: LDS [32][32] row-major [in][out].
-// Each of the 4 waves owns tiles wid, wid+4, ... of (rows_pad/16 × 2).
-DEV_INLINE void gemm_acc(const float* __restrict__ src,
-                         float* __restrict__ dst,
-                         const float* __restrict__ W, bool transposeW,
-                         int rows_pad, int tid) {
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int nw = blockDim.x >> 6;
-    const int mtiles = rows_pad / 16;
-    const int r_in = lane & 15;          // A-operand row within tile
-    const int k_in = lane >> 4;          // A/B k index (0..3)
-    for (int t = wid; t < mtiles * 2; t += nw) {
-        const int mt = t >> 1;
-        const int c0 = (t & 1) * 16;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < F / 4; ++kk) {
-            const int k = kk * 4 + k_in;
-            const float a = src[(mt * 16 + r_in) * STRIDE + k];
-            const float b = transposeW ? W[(c0 + r_in) * F + k]
-                                       : W[k * F + c0 + r_in];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-        }
-        // C layout: col = lane&15, row = (lane>>4)*4 + reg
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = mt * 16 + (lane >> 4) * 4 + r;
-            dst[row * STRIDE + c0 + (lane & 15)] += acc[r];
-        }
-    }
-}
-
-// ---- weight-gradient tile: dW[i][j] = sum_r src[r][i] * delta[r][j] ------
-// MFMA over the row (K) dimension: 2×2 tiles of 16×16, one per wave.
-DEV_INLINE void gemm_wgrad(const float* __restrict__ src,
-                           const float* __restrict__ delta,
-                           float* __restrict__ dw_out,  // global [32][32]
-                           int rows_pad, int tid) {
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int nw = blockDim.x >> 6;
-    const int k_in = lane >> 4;
-    const int c_in = lane & 15;
-    // 4 output tiles × 2 row-range halves keeps all 8 waves busy; the two
-    // halves combine through global fp32 atomics (dW is prezeroed)
-    for (int t = wid; t < 8; t += nw) {
-        const int tile = t >> 1, half = t & 1;
-        const int i0 = (tile >> 1) * 16, j0 = (tile & 1) * 16;
-        const int kk0 = half * (rows_pad / 8);
-        const int kk1 = kk0 + rows_pad / 8;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int kk = kk0; kk < kk1; ++kk) {
-            const int r = kk * 4 + k_in;
-            const float a = src[r * STRIDE + i0 + c_in];
-            const float b = delta[r * STRIDE + j0 + c_in];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            atomicAdd(&dw_out[(i0 + (lane >> 4) * 4 + r) * F + j0
-                              + (lane & 15)], acc[r]);
-    }
-}
+// 4 output tiles × 2 row-range halves keeps all 8 waves busy
+constexpr int WGRAD_SPLIT = 2;
 
 // ---- fused layer tile: Xb <- act(X·W0 + T·W1 + b) -----------------------
 // Safe in place: every tile's A-operands read only the tile's own rows, so
@@ -133,9 +74,7 @@ DEV_INLINE void gemm_layer_fused(float* __restrict__ Xb,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = mt * 16 + (lane >> 4) * 4 + r;
-            float y = acc[r] + bv;
-            y = last ? (y > 0.f ? y : 0.f) : (y > 0.f ? y : 0.2f * y);
-            Xb[row * STRIDE + col] = y;
+            Xb[row * STRIDE + col] = act(acc[r] + bv, last);
         }
     }
 }
@@ -174,36 +113,6 @@ DEV_INLINE void gemm_dx_fused(const float* __restrict__ Db,
             Ab[row * STRIDE + col] = acc0[r];
             if (K > 1) Tb[row * STRIDE + col] = acc1[r];
         }
-    }
-}
-
-// ---- activation tile <-> global copies (coalesced, float4 on global) -----
-// LDS rows have stride 33 (misaligned for vector LDS ops); global rows are
-// dense F=32 floats, 16B-aligned.  Task split (row, 4-col group) puts
-// consecutive lanes on consecutive 16B global segments.
-DEV_INLINE void store_acts(const float* __restrict__ lds,
-                           float* __restrict__ gmem, int Ee, int tid,
-                           int nt) {
-    for (int t = tid; t < Ee * (F / 4); t += nt) {
-        const int r = t >> 3;
-        const int c = (t & 7) * 4;
-        const float* s = lds + r * STRIDE + c;
-        float4 v = {s[0], s[1], s[2], s[3]};
-        *reinterpret_cast<float4*>(gmem + (size_t)r * F + c) = v;
-    }
-}
-
-DEV_INLINE void load_acts(float* __restrict__ lds,
-                          const float* __restrict__ gmem, int Ee,
-                          int rows_pad, int tid, int nt) {
-    for (int t = tid; t < rows_pad * (F / 4); t += nt) {
-        const int r = t >> 3;
-        const int c = (t & 7) * 4;
-        float4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r < Ee)
-            v = *reinterpret_cast<const float4*>(gmem + (size_t)r * F + c);
-        float* d = lds + r * STRIDE + c;
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
     }
 }
 
@@ -291,9 +200,57 @@ DEV_INLINE void bias_act_rows(const float* __restrict__ src,
                               int rows_pad, int tid, int nt) {
     for (int t = tid; t < rows_pad * F; t += nt) {
         const int r = t / F, c = t % F;
-        float y = src[r * STRIDE + c] + bl[c];
-        y = last ? (y > 0.f ? y : 0.f) : (y > 0.f ? y : 0.2f * y);
-        dst[r * STRIDE + c] = y;
+        dst[r * STRIDE + c] = act(src[r * STRIDE + c] + bl[c], last);
+    }
+}
+
+// ---- kernel prologue, shared by the K<=2 and the generic-K kernels -------
+// Point ipt/cls at graph b's support CSR.  With stage_csr the CSR is copied
+// into LDS at `lds` first: it is read by every SpMV of every layer, and
+// latency-bound global gathers otherwise dominate.  The caller's first
+// barrier covers the copy.
+DEV_INLINE void graph_csr(const int* __restrict__ ext_indptr,
+                          const long* __restrict__ ext_base,
+                          const int* __restrict__ ext_cols, int b, int Ee,
+                          int stage_csr, int* __restrict__ lds, int tid,
+                          int nt, const int*& ipt, const int*& cls) {
+    ipt = ext_indptr + (size_t)b * (Ee + 1);
+    cls = ext_cols + ext_base[b];
+    if (stage_csr) {
+        int* l_ipt = lds;
+        int* l_cols = l_ipt + (Ee + 1);
+        for (int i = tid; i < Ee + 1; i += nt) l_ipt[i] = ipt[i];
+        const int nnz = ipt[Ee];
+        for (int i = tid; i < nnz; i += nt) l_cols[i] = cls[i];
+        ipt = l_ipt;
+        cls = l_cols;
+    }
+}
+
+// Xb <- features of one graph: 4 real cols as one float4, the rest (and the
+// padded rows) zero
+DEV_INLINE void load_features(float* __restrict__ Xb,
+                              const float* __restrict__ xb, int Ee,
+                              int rows_pad, int tid, int nt) {
+    for (int r = tid; r < rows_pad; r += nt) {
+        float* row = Xb + r * STRIDE;
+        for (int c = 0; c < F; ++c) row[c] = 0.f;
+        if (r < Ee) {
+            const float4 v =
+                *reinterpret_cast<const float4*>(xb + (size_t)r * 4);
+            row[0] = v.x; row[1] = v.y; row[2] = v.z; row[3] = v.w;
+        }
+    }
+}
+
+// Db <- top delta of one graph: only column 0 carries dλ
+DEV_INLINE void load_top_delta(float* __restrict__ Db,
+                               const float* __restrict__ dlamb, int Ee,
+                               int rows_pad, int tid, int nt) {
+    for (int r = tid; r < rows_pad; r += nt) {
+        float* row = Db + r * STRIDE;
+        for (int c = 0; c < F; ++c) row[c] = 0.f;
+        if (r < Ee) row[0] = dlamb[r];
     }
 }
 
@@ -311,8 +268,7 @@ __global__ void cheb_fwd_kernel(
     float* __restrict__ acts,            // (B,L+1,Ee,32) out
     float* __restrict__ t1s,             // (B,L,Ee,32) out: A·X per layer
     float* __restrict__ lam,             // (B,Ee) out
-    int B, int Ee, int L, int K, int rows_pad, int max_nnz,
-    int stage_csr) {
+    int Ee, int L, int K, int rows_pad, int stage_csr) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* Xb = reinterpret_cast<float*>(smem_raw);
     float* Tb = Xb + (size_t)rows_pad * STRIDE;
@@ -321,34 +277,14 @@ __global__ void cheb_fwd_kernel(
 
     const int b = blockIdx.x;
     const int tid = threadIdx.x, nt = blockDim.x;
-    const int* ipt = ext_indptr + (size_t)b * (Ee + 1);
-    const int* cls = ext_cols + ext_base[b];
-    if (stage_csr) {
-        // the support CSR is read by every SpMV of every layer — stage it
-        // in LDS once (latency-bound global gathers otherwise dominate)
-        int* l_ipt = reinterpret_cast<int*>(bl + F);
-        int* l_cols = l_ipt + (Ee + 1);
-        for (int i = tid; i < Ee + 1; i += nt) l_ipt[i] = ipt[i];
-        const int nnz = ipt[Ee];
-        for (int i = tid; i < nnz; i += nt) l_cols[i] = cls[i];
-        ipt = l_ipt;
-        cls = l_cols;
-    }
-    const float* xb = x_in + (size_t)b * Ee * 4;
+    const int *ipt, *cls;
+    graph_csr(ext_indptr, ext_base, ext_cols, b, Ee, stage_csr,
+              reinterpret_cast<int*>(bl + F), tid, nt, ipt, cls);
     float* actsb = acts + (size_t)b * (L + 1) * Ee * F;
 
-    // load features (4 real cols as one float4, rest zero)
-    for (int r = tid; r < rows_pad; r += nt) {
-        float* row = Xb + r * STRIDE;
-        for (int c = 0; c < F; ++c) row[c] = 0.f;
-        if (r < Ee) {
-            const float4 v =
-                *reinterpret_cast<const float4*>(xb + (size_t)r * 4);
-            row[0] = v.x; row[1] = v.y; row[2] = v.z; row[3] = v.w;
-        }
-    }
+    load_features(Xb, x_in + (size_t)b * Ee * 4, Ee, rows_pad, tid, nt);
     __syncthreads();
-    store_acts(Xb, actsb, Ee, tid, nt);
+    store_rows(Xb, actsb, 0, Ee, Ee, tid, nt);
 
     for (int l = 0; l < L; ++l) {
         // stage weights + bias
@@ -360,12 +296,14 @@ __global__ void cheb_fwd_kernel(
             spmv(Xb, Tb, ipt, cls, Ee, rows_pad, tid, nt, 0); // T1 = A·X
             __syncthreads();
             // save T1 for the backward weight-gradient pass
-            store_acts(Tb, t1s + ((size_t)b * L + l) * Ee * F, Ee, tid, nt);
+            store_rows(Tb, t1s + ((size_t)b * L + l) * Ee * F, 0, Ee,
+                       Ee, tid, nt);
         }
         // in-register tile product + activation, written back into Xb
         gemm_layer_fused(Xb, Tb, Wl, bl, K, l == L - 1, rows_pad, tid);
         __syncthreads();
-        store_acts(Xb, actsb + (size_t)(l + 1) * Ee * F, Ee, tid, nt);
+        store_rows(Xb, actsb + (size_t)(l + 1) * Ee * F, 0, Ee, Ee,
+                   tid, nt);
         __syncthreads();
     }
     for (int r = tid; r < Ee; r += nt) lam[(size_t)b * Ee + r] =
@@ -378,7 +316,7 @@ __global__ void cheb_fwd_kernel(
 // LDS: Ab | Db | Tb | Wl | scratch
 // ---------------------------------------------------------------------------
 // stage_mask (timing ablation only — outputs are wrong unless 0xF):
-// bit0 act-mask+db, bit1 load_acts+wgrads, bit2 dx gemm, bit3 spmv
+// bit0 act-mask+db, bit1 load_rows+wgrads, bit2 dx gemm, bit3 spmv
 __global__ void cheb_bwd_kernel(
     const float* __restrict__ dlam,      // (B,Ee)
     const float* __restrict__ acts,      // (B,L+1,Ee,32)
@@ -389,8 +327,7 @@ __global__ void cheb_bwd_kernel(
     const int* __restrict__ ext_cols,
     float* __restrict__ dW,              // (B,L,K,32,32) out (prezeroed)
     float* __restrict__ db,              // (B,L,32) out (prezeroed)
-    int B, int Ee, int L, int K, int rows_pad, int max_nnz,
-    int stage_csr, int stage_mask) {
+    int Ee, int L, int K, int rows_pad, int stage_csr, int stage_mask) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* Ab = reinterpret_cast<float*>(smem_raw);   // X_l, later dX
     float* Db = Ab + (size_t)rows_pad * STRIDE;       // current delta
@@ -399,77 +336,51 @@ __global__ void cheb_bwd_kernel(
 
     const int b = blockIdx.x;
     const int tid = threadIdx.x, nt = blockDim.x;
-    const int* ipt = ext_indptr + (size_t)b * (Ee + 1);
-    const int* cls = ext_cols + ext_base[b];
-    if (stage_csr) {
-        int* l_ipt = reinterpret_cast<int*>(Wl + (size_t)K * F * F);
-        int* l_cols = l_ipt + (Ee + 1);
-        for (int i = tid; i < Ee + 1; i += nt) l_ipt[i] = ipt[i];
-        const int nnz = ipt[Ee];
-        for (int i = tid; i < nnz; i += nt) l_cols[i] = cls[i];
-        ipt = l_ipt;
-        cls = l_cols;
-    }
+    const int *ipt, *cls;
+    graph_csr(ext_indptr, ext_base, ext_cols, b, Ee, stage_csr,
+              reinterpret_cast<int*>(Wl + (size_t)K * F * F), tid, nt, ipt,
+              cls);
     const float* actsb = acts + (size_t)b * (L + 1) * Ee * F;
     float* dWb = dW + (size_t)b * L * K * F * F;
     float* dbb = db + (size_t)b * L * F;
 
-    // top delta: only column 0 carries dλ
-    for (int r = tid; r < rows_pad; r += nt) {
-        float* row = Db + r * STRIDE;
-        for (int c = 0; c < F; ++c) row[c] = 0.f;
-        if (r < Ee) row[0] = dlam[(size_t)b * Ee + r];
-    }
+    load_top_delta(Db, dlam + (size_t)b * Ee, Ee, rows_pad, tid, nt);
     __syncthreads();
 
     for (int l = L - 1; l >= 0; --l) {
         const bool last = (l == L - 1);
         // activation mask from stored post-act X_{l+1} (coalesced float4)
-        const float slope = last ? 0.f : 0.2f;
         if (stage_mask & 1)
-        for (int t = tid; t < Ee * (F / 4); t += nt) {
-            const int r = t >> 3;
-            const int c = (t & 7) * 4;
-            const float4 v = *reinterpret_cast<const float4*>(
-                actsb + ((size_t)(l + 1) * Ee + r) * F + c);
-            float* d = Db + r * STRIDE + c;
-            d[0] *= v.x > 0.f ? 1.f : slope;
-            d[1] *= v.y > 0.f ? 1.f : slope;
-            d[2] *= v.z > 0.f ? 1.f : slope;
-            d[3] *= v.w > 0.f ? 1.f : slope;
-        }
+            mask_rows(Db, actsb + (size_t)(l + 1) * Ee * F, Ee,
+                      last ? 0.f : 0.2f, tid, nt);
         // load X_l  (feeding the wgrad MFMA tiles straight from global
         // was MEASURED 2x slower — dependent-accumulator stalls on the
         // ~400-cycle loads; and folding db into the mask sweep above was
         // measured +13% — atomic flush every column-group change.
         // profiles/r02_notes.md: measure, don't guess.)
         if (stage_mask & 2)
-            load_acts(Ab, actsb + (size_t)l * Ee * F, Ee, rows_pad, tid, nt);
+            load_rows(Ab, actsb + (size_t)l * Ee * F, 0, rows_pad, Ee, tid,
+                      nt);
         for (int i = tid; i < K * F * F; i += nt)
             Wl[i] = W[((size_t)l * K) * F * F + i];
         __syncthreads();
 
-        // db[j] = sum_r Db[r][j] — (j, row-chunk) threads, db prezeroed
-        if (stage_mask & 1) {
-            const int nchunk = nt / F;
-            const int j = tid % F, ch = tid / F;
-            float acc = 0.f;
-            for (int r = ch; r < Ee; r += nchunk) acc += Db[r * STRIDE + j];
-            atomicAdd(&dbb[l * F + j], acc);
-        }
+        if (stage_mask & 1) db_colsum(Db, Ee, dbb + l * F, tid, nt);
         if (stage_mask & 2) {
             if (K > 1)
                 // issue the T1 staging loads BEFORE wgrad0: disjoint sets
                 // (reads t1s/global, writes Tb rows vs wgrad0's Ab/Db
                 // reads + dW atomics), so no barrier between them — the
                 // global-load latency hides under the wgrad0 MFMA work
-                load_acts(Tb, t1s + ((size_t)b * L + l) * Ee * F, Ee,
-                          rows_pad, tid, nt);             // T1 from forward
-            gemm_wgrad(Ab, Db, dWb + ((size_t)l * K) * F * F, rows_pad, tid);
+                load_rows(Tb, t1s + ((size_t)b * L + l) * Ee * F, 0,
+                          rows_pad, Ee, tid, nt);         // T1 from forward
+            wgrad_rows<WGRAD_SPLIT>(Ab, Db, dWb + ((size_t)l * K) * F * F,
+                                    rows_pad, tid);
             if (K > 1) {
                 __syncthreads();
-                gemm_wgrad(Tb, Db, dWb + ((size_t)l * K + 1) * F * F,
-                           rows_pad, tid);
+                wgrad_rows<WGRAD_SPLIT>(Tb, Db,
+                                        dWb + ((size_t)l * K + 1) * F * F,
+                                        rows_pad, tid);
             }
         }
         if (l == 0) break;                       // features are leaves
@@ -520,32 +431,15 @@ __global__ void cheb_kn_fwd_kernel(
 
     const int b = blockIdx.x;
     const int tid = threadIdx.x, nt = blockDim.x;
-    const int* ipt = ext_indptr + (size_t)b * (Ee + 1);
-    const int* cls = ext_cols + ext_base[b];
-    if (stage_csr) {
-        int* l_ipt = reinterpret_cast<int*>(bl + F);
-        int* l_cols = l_ipt + (Ee + 1);
-        for (int i = tid; i < Ee + 1; i += nt) l_ipt[i] = ipt[i];
-        const int nnz = ipt[Ee];
-        for (int i = tid; i < nnz; i += nt) l_cols[i] = cls[i];
-        ipt = l_ipt;
-        cls = l_cols;
-    }
-    const float* xb = x_in + (size_t)b * Ee * 4;
+    const int *ipt, *cls;
+    graph_csr(ext_indptr, ext_base, ext_cols, b, Ee, stage_csr,
+              reinterpret_cast<int*>(bl + F), tid, nt, ipt, cls);
     float* actsb = acts + (size_t)b * (L + 1) * Ee * F;
     float* tksb = tks + (size_t)b * L * (K - 1) * Ee * F;
 
-    for (int r = tid; r < rows_pad; r += nt) {
-        float* row = Xb + r * STRIDE;
-        for (int c = 0; c < F; ++c) row[c] = 0.f;
-        if (r < Ee) {
-            const float4 v =
-                *reinterpret_cast<const float4*>(xb + (size_t)r * 4);
-            row[0] = v.x; row[1] = v.y; row[2] = v.z; row[3] = v.w;
-        }
-    }
+    load_features(Xb, x_in + (size_t)b * Ee * 4, Ee, rows_pad, tid, nt);
     __syncthreads();
-    store_acts(Xb, actsb, Ee, tid, nt);
+    store_rows(Xb, actsb, 0, Ee, Ee, tid, nt);
 
     for (int l = 0; l < L; ++l) {
         for (int i = tid; i < K * F * F; i += nt)
@@ -553,11 +447,12 @@ __global__ void cheb_kn_fwd_kernel(
         for (int i = tid; i < F; i += nt) bl[i] = bias[l * F + i];
         zero_rows(Yb, rows_pad, tid, nt);
         __syncthreads();
-        gemm_acc(Xb, Yb, Wl, false, rows_pad, tid);           // T0·W0
+        gemm_rows(Xb, Yb, Wl, false, rows_pad, tid);          // T0·W0
         spmv(Xb, Tb, ipt, cls, Ee, rows_pad, tid, nt, 0);     // T1 = A·X
         __syncthreads();
-        store_acts(Tb, tksb + (size_t)l * (K - 1) * Ee * F, Ee, tid, nt);
-        gemm_acc(Tb, Yb, Wl + F * F, false, rows_pad, tid);   // T1·W1
+        store_rows(Tb, tksb + (size_t)l * (K - 1) * Ee * F, 0, Ee, Ee,
+                   tid, nt);
+        gemm_rows(Tb, Yb, Wl + F * F, false, rows_pad, tid);  // T1·W1
         float* prev = Xb;                                     // T_{k-2}
         float* cur = Tb;                                      // T_{k-1}
         for (int k = 2; k < K; ++k) {
@@ -565,14 +460,16 @@ __global__ void cheb_kn_fwd_kernel(
             spmv(cur, prev, ipt, cls, Ee, rows_pad, tid, nt, 2);
             __syncthreads();
             float* t = prev; prev = cur; cur = t;             // cur = T_k
-            store_acts(cur, tksb + ((size_t)l * (K - 1) + k - 1) * Ee * F,
-                       Ee, tid, nt);
-            gemm_acc(cur, Yb, Wl + (size_t)k * F * F, false, rows_pad, tid);
+            store_rows(cur, tksb + ((size_t)l * (K - 1) + k - 1) * Ee * F,
+                       0, Ee, Ee, tid, nt);
+            gemm_rows(cur, Yb, Wl + (size_t)k * F * F, false, rows_pad,
+                      tid);
         }
         __syncthreads();
         bias_act_rows(Yb, Xb, bl, l == L - 1, rows_pad, tid, nt);
         __syncthreads();
-        store_acts(Xb, actsb + (size_t)(l + 1) * Ee * F, Ee, tid, nt);
+        store_rows(Xb, actsb + (size_t)(l + 1) * Ee * F, 0, Ee, Ee,
+                   tid, nt);
         __syncthreads();
     }
     for (int r = tid; r < Ee; r += nt) lam[(size_t)b * Ee + r] =
@@ -598,64 +495,39 @@ __global__ void cheb_kn_bwd_kernel(
 
     const int b = blockIdx.x;
     const int tid = threadIdx.x, nt = blockDim.x;
-    const int* ipt = ext_indptr + (size_t)b * (Ee + 1);
-    const int* cls = ext_cols + ext_base[b];
-    if (stage_csr) {
-        int* l_ipt = reinterpret_cast<int*>(Wl + (size_t)K * F * F);
-        int* l_cols = l_ipt + (Ee + 1);
-        for (int i = tid; i < Ee + 1; i += nt) l_ipt[i] = ipt[i];
-        const int nnz = ipt[Ee];
-        for (int i = tid; i < nnz; i += nt) l_cols[i] = cls[i];
-        ipt = l_ipt;
-        cls = l_cols;
-    }
+    const int *ipt, *cls;
+    graph_csr(ext_indptr, ext_base, ext_cols, b, Ee, stage_csr,
+              reinterpret_cast<int*>(Wl + (size_t)K * F * F), tid, nt, ipt,
+              cls);
     const float* actsb = acts + (size_t)b * (L + 1) * Ee * F;
     const float* tksb = tks + (size_t)b * L * (K - 1) * Ee * F;
     float* dWb = dW + (size_t)b * L * K * F * F;
     float* dbb = db + (size_t)b * L * F;
 
-    for (int r = tid; r < rows_pad; r += nt) {
-        float* row = Db + r * STRIDE;
-        for (int c = 0; c < F; ++c) row[c] = 0.f;
-        if (r < Ee) row[0] = dlam[(size_t)b * Ee + r];
-    }
+    load_top_delta(Db, dlam + (size_t)b * Ee, Ee, rows_pad, tid, nt);
     __syncthreads();
 
     for (int l = L - 1; l >= 0; --l) {
         const bool last = (l == L - 1);
-        const float slope = last ? 0.f : 0.2f;
-        for (int t = tid; t < Ee * (F / 4); t += nt) {
-            const int r = t >> 3;
-            const int c = (t & 7) * 4;
-            const float4 v = *reinterpret_cast<const float4*>(
-                actsb + ((size_t)(l + 1) * Ee + r) * F + c);
-            float* d = Db + r * STRIDE + c;
-            d[0] *= v.x > 0.f ? 1.f : slope;
-            d[1] *= v.y > 0.f ? 1.f : slope;
-            d[2] *= v.z > 0.f ? 1.f : slope;
-            d[3] *= v.w > 0.f ? 1.f : slope;
-        }
+        mask_rows(Db, actsb + (size_t)(l + 1) * Ee * F, Ee,
+                  last ? 0.f : 0.2f, tid, nt);
         for (int i = tid; i < K * F * F; i += nt)
             Wl[i] = W[((size_t)l * K) * F * F + i];
         __syncthreads();
-        {   // db[j] = sum_r Db[r][j]
-            const int nchunk = nt / F;
-            const int j = tid % F, ch = tid / F;
-            float acc = 0.f;
-            for (int r = ch; r < Ee; r += nchunk) acc += Db[r * STRIDE + j];
-            atomicAdd(&dbb[l * F + j], acc);
-        }
+        db_colsum(Db, Ee, dbb + l * F, tid, nt);
         // weight gradients: dW_k = T_kᵀ·Db, T_k streamed through Pb
-        load_acts(Pb, actsb + (size_t)l * Ee * F, Ee, rows_pad, tid, nt);
+        load_rows(Pb, actsb + (size_t)l * Ee * F, 0, rows_pad, Ee, tid, nt);
         __syncthreads();
-        gemm_wgrad(Pb, Db, dWb + ((size_t)l * K) * F * F, rows_pad, tid);
+        wgrad_rows<WGRAD_SPLIT>(Pb, Db, dWb + ((size_t)l * K) * F * F,
+                                rows_pad, tid);
         for (int k = 1; k < K; ++k) {
             __syncthreads();
-            load_acts(Pb, tksb + ((size_t)l * (K - 1) + k - 1) * Ee * F,
-                      Ee, rows_pad, tid, nt);
+            load_rows(Pb, tksb + ((size_t)l * (K - 1) + k - 1) * Ee * F, 0,
+                      rows_pad, Ee, tid, nt);
             __syncthreads();
-            gemm_wgrad(Pb, Db, dWb + ((size_t)l * K + k) * F * F, rows_pad,
-                       tid);
+            wgrad_rows<WGRAD_SPLIT>(Pb, Db,
+                                    dWb + ((size_t)l * K + k) * F * F,
+                                    rows_pad, tid);
         }
         if (l == 0) break;
         __syncthreads();
@@ -664,16 +536,16 @@ __global__ void cheb_kn_bwd_kernel(
         zero_rows(Qb, rows_pad, tid, nt);
         __syncthreads();
         if (K == 1) {
-            gemm_acc(Db, Pb, Wl, true, rows_pad, tid);        // ĝ_0
+            gemm_rows(Db, Pb, Wl, true, rows_pad, tid);        // ĝ_0
             __syncthreads();
             // dX = ĝ_0 → copy into Db
             for (int t = tid; t < rows_pad * F; t += nt)
                 Db[(t / F) * STRIDE + (t % F)] =
                     Pb[(t / F) * STRIDE + (t % F)];
         } else {
-            gemm_acc(Db, Pb, Wl + (size_t)(K - 1) * F * F, true, rows_pad,
+            gemm_rows(Db, Pb, Wl + (size_t)(K - 1) * F * F, true, rows_pad,
                      tid);                                    // ĝ_{K-1}
-            gemm_acc(Db, Qb, Wl + (size_t)(K - 2) * F * F, true, rows_pad,
+            gemm_rows(Db, Qb, Wl + (size_t)(K - 2) * F * F, true, rows_pad,
                      tid);                                    // ĝ_{K-2} base
             float* cur = Pb;
             float* prv = Qb;
@@ -683,7 +555,7 @@ __global__ void cheb_kn_bwd_kernel(
                 __syncthreads();
                 negate_rows(cur, rows_pad, tid, nt);          // −ĝ_k
                 __syncthreads();
-                gemm_acc(Db, cur, Wl + (size_t)(k - 2) * F * F, true,
+                gemm_rows(Db, cur, Wl + (size_t)(k - 2) * F * F, true,
                          rows_pad, tid);                      // + base_{k-2}
                 float* t = cur; cur = prv; prv = t;           // cur=ĝ_{k-1}
             }
@@ -699,7 +571,13 @@ __global__ void cheb_kn_bwd_kernel(
 
 }  // namespace
 
-static int round16(int x) { return (x + 15) & ~15; }
+// Does a graph of Ee extended links run on the LDS-resident kernels of this
+// K, forward and backward?  The Python side routes on this.
+bool cheb_fits_lds(long Ee, long K) {
+    const bool kn = K > 2;
+    return cheb_lds_plan(Ee, K, kn ? KN_NBUF : FWD_NBUF, true, 0).fits &&
+           cheb_lds_plan(Ee, K, kn ? KN_NBUF : BWD_NBUF, false, 0).fits;
+}
 
 std::vector<torch::Tensor> cheb_fwd_hip(
     torch::Tensor x, torch::Tensor W, torch::Tensor bias,
@@ -708,25 +586,20 @@ std::vector<torch::Tensor> cheb_fwd_hip(
     const int B = x.size(0), Ee = x.size(1);
     const int L = W.size(0), K = W.size(1);
     TORCH_CHECK(K <= 2, "fused ChebConv kernel supports K<=2");
-    const int rows_pad = round16(Ee);
+    const LdsPlan plan = cheb_lds_plan(Ee, K, FWD_NBUF, true, max_nnz);
+    TORCH_CHECK(plan.fits, "graph too large for fused ChebConv");
     auto acts = torch::empty({B, L + 1, Ee, F}, x.options());
     auto t1s = torch::empty({B, L, Ee, F}, x.options());
     auto lam = torch::empty({B, Ee}, x.options());
-    size_t lds = sizeof(float) *
-        (2 * (size_t)rows_pad * STRIDE + (size_t)K * F * F + F);
-    TORCH_CHECK(lds <= 160 * 1024, "graph too large for fused ChebConv");
-    const size_t csr_bytes = sizeof(int) * ((size_t)Ee + 1 + max_nnz);
-    const int stage_csr = (lds + csr_bytes <= 160 * 1024) ? 1 : 0;
-    if (stage_csr) lds += csr_bytes;
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(cheb_fwd_kernel, dim3(B), dim3(512), lds,
+    hipLaunchKernelGGL(cheb_fwd_kernel, dim3(B), dim3(512), plan.lds_bytes,
                        stream.stream(),
                        x.data_ptr<float>(), W.data_ptr<float>(),
                        bias.data_ptr<float>(), ext_indptr.data_ptr<int>(),
                        ext_base.data_ptr<long>(), ext_cols.data_ptr<int>(),
                        acts.data_ptr<float>(), t1s.data_ptr<float>(),
                        lam.data_ptr<float>(),
-                       B, Ee, L, K, rows_pad, (int)max_nnz, stage_csr);
+                       Ee, L, K, plan.rows_pad, plan.stage_csr);
     return {lam, acts, t1s};
 }
 
@@ -737,26 +610,21 @@ std::vector<torch::Tensor> cheb_kn_fwd_hip(
     const int B = x.size(0), Ee = x.size(1);
     const int L = W.size(0), K = W.size(1);
     TORCH_CHECK(K >= 2, "generic-K ChebConv kernel expects K>=2");
-    const int rows_pad = round16(Ee);
+    const LdsPlan plan = cheb_lds_plan(Ee, K, KN_NBUF, true, max_nnz);
+    TORCH_CHECK(plan.fits,
+                "graph too large for generic-K fused ChebConv (LDS)");
     auto acts = torch::empty({B, L + 1, Ee, F}, x.options());
     auto tks = torch::empty({B, L, K - 1, Ee, F}, x.options());
     auto lam = torch::empty({B, Ee}, x.options());
-    size_t lds = sizeof(float) *
-        (3 * (size_t)rows_pad * STRIDE + (size_t)K * F * F + F);
-    TORCH_CHECK(lds <= 160 * 1024,
-                "graph too large for generic-K fused ChebConv (LDS)");
-    const size_t csr_bytes = sizeof(int) * ((size_t)Ee + 1 + max_nnz);
-    const int stage_csr = (lds + csr_bytes <= 160 * 1024) ? 1 : 0;
-    if (stage_csr) lds += csr_bytes;
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(cheb_kn_fwd_kernel, dim3(B), dim3(512), lds,
-                       stream.stream(),
+    hipLaunchKernelGGL(cheb_kn_fwd_kernel, dim3(B), dim3(512),
+                       plan.lds_bytes, stream.stream(),
                        x.data_ptr<float>(), W.data_ptr<float>(),
                        bias.data_ptr<float>(), ext_indptr.data_ptr<int>(),
                        ext_base.data_ptr<long>(), ext_cols.data_ptr<int>(),
                        acts.data_ptr<float>(), tks.data_ptr<float>(),
                        lam.data_ptr<float>(),
-                       B, Ee, L, K, rows_pad, stage_csr);
+                       B, Ee, L, K, plan.rows_pad, plan.stage_csr);
     return {lam, acts, tks};
 }
 
@@ -766,25 +634,20 @@ std::vector<torch::Tensor> cheb_kn_bwd_hip(
     torch::Tensor ext_cols, long max_nnz) {
     const int B = dlam.size(0), Ee = dlam.size(1);
     const int L = W.size(0), K = W.size(1);
-    const int rows_pad = round16(Ee);
+    const LdsPlan plan = cheb_lds_plan(Ee, K, KN_NBUF, false, max_nnz);
+    TORCH_CHECK(plan.fits,
+                "graph too large for generic-K fused ChebConv bwd (LDS)");
     auto dW = torch::zeros({B, L, K, F, F}, dlam.options());
     auto db = torch::zeros({B, L, F}, dlam.options());
-    size_t lds = sizeof(float) *
-        (3 * (size_t)rows_pad * STRIDE + (size_t)K * F * F);
-    TORCH_CHECK(lds <= 160 * 1024,
-                "graph too large for generic-K fused ChebConv bwd (LDS)");
-    const size_t csr_bytes = sizeof(int) * ((size_t)Ee + 1 + max_nnz);
-    const int stage_csr = (lds + csr_bytes <= 160 * 1024) ? 1 : 0;
-    if (stage_csr) lds += csr_bytes;
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(cheb_kn_bwd_kernel, dim3(B), dim3(512), lds,
-                       stream.stream(),
+    hipLaunchKernelGGL(cheb_kn_bwd_kernel, dim3(B), dim3(512),
+                       plan.lds_bytes, stream.stream(),
                        dlam.data_ptr<float>(), acts.data_ptr<float>(),
                        tks.data_ptr<float>(), W.data_ptr<float>(),
                        ext_indptr.data_ptr<int>(), ext_base.data_ptr<long>(),
                        ext_cols.data_ptr<int>(),
                        dW.data_ptr<float>(), db.data_ptr<float>(),
-                       B, Ee, L, K, rows_pad, stage_csr);
+                       B, Ee, L, K, plan.rows_pad, plan.stage_csr);
     return {dW, db};
 }
 
@@ -794,24 +657,19 @@ std::vector<torch::Tensor> cheb_bwd_hip_mask(
     torch::Tensor ext_cols, long max_nnz, long stage_mask) {
     const int B = dlam.size(0), Ee = dlam.size(1);
     const int L = W.size(0), K = W.size(1);
-    const int rows_pad = round16(Ee);
+    const LdsPlan plan = cheb_lds_plan(Ee, K, BWD_NBUF, false, max_nnz);
+    TORCH_CHECK(plan.fits, "graph too large for fused ChebConv bwd");
     auto dW = torch::zeros({B, L, K, F, F}, dlam.options());
     auto db = torch::zeros({B, L, F}, dlam.options());
-    size_t lds = sizeof(float) *
-        (3 * (size_t)rows_pad * STRIDE + (size_t)K * F * F);
-    TORCH_CHECK(lds <= 160 * 1024, "graph too large for fused ChebConv bwd");
-    const size_t csr_bytes = sizeof(int) * ((size_t)Ee + 1 + max_nnz);
-    const int stage_csr = (lds + csr_bytes <= 160 * 1024) ? 1 : 0;
-    if (stage_csr) lds += csr_bytes;
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(cheb_bwd_kernel, dim3(B), dim3(512), lds,
+    hipLaunchKernelGGL(cheb_bwd_kernel, dim3(B), dim3(512), plan.lds_bytes,
                        stream.stream(),
                        dlam.data_ptr<float>(), acts.data_ptr<float>(),
                        t1s.data_ptr<float>(),
                        W.data_ptr<float>(), ext_indptr.data_ptr<int>(),
                        ext_base.data_ptr<long>(), ext_cols.data_ptr<int>(),
                        dW.data_ptr<float>(), db.data_ptr<float>(),
-                       B, Ee, L, K, rows_pad, (int)max_nnz, stage_csr,
+                       Ee, L, K, plan.rows_pad, plan.stage_csr,
                        (int)stage_mask);
     return {dW, db};
 }

@@ -5,21 +5,21 @@
 // resident at these sizes); each block owns a 64-row tile of one graph and
 // stages its X tile + the SpMV result tile in LDS (~42 KB → 3 blocks/CU).
 // The dense products run on the same mfma_f32_16x16x4 tiles as the
-// LDS-resident kernel.  One launch per layer forward; two per layer
-// backward (the dX SpMV needs the full U = δ·W1ᵀ materialized first).
+// LDS-resident kernel (cheb_tiles.h).  One launch per layer forward; two
+// per layer backward (the dX SpMV needs the full U = δ·W1ᵀ materialized
+// first).
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include "cheb_tiles.h"
+
 namespace {
 
-#define DEV_INLINE __device__ __forceinline__
+using namespace cheb;
 
-constexpr int F = 32;
 constexpr int RT = 64;         // rows per tile
-constexpr int STRIDE = 33;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // dst_tile(LDS, RT×STRIDE) = rows [r0, r0+RT) of (A · src_global)
 DEV_INLINE void spmv_tile(const float* __restrict__ src, float* __restrict__
@@ -31,83 +31,9 @@ DEV_INLINE void spmv_tile(const float* __restrict__ src, float* __restrict__
         const int c0 = (task & 7) * 4;
         const int r = r0 + rr;
         float4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (r < Ee) {
-            for (int a = indptr[r]; a < indptr[r + 1]; ++a) {
-                const float4 v = *reinterpret_cast<const float4*>(
-                    src + (size_t)cols[a] * F + c0);
-                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-            }
-        }
+        if (r < Ee) acc = csr_gather4(src, indptr, cols, r, c0);
         float* d = dst + rr * STRIDE + c0;
         d[0] = acc.x; d[1] = acc.y; d[2] = acc.z; d[3] = acc.w;
-    }
-}
-
-// load a 64-row tile from global (B?,Ee,32) into LDS (RT×STRIDE)
-DEV_INLINE void load_tile(const float* __restrict__ src, float* __restrict__
-                          dst, int r0, int Ee, int tid, int nt) {
-    for (int task = tid; task < RT * (F / 4); task += nt) {
-        const int rr = task >> 3;
-        const int c0 = (task & 7) * 4;
-        float4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r0 + rr < Ee)
-            v = *reinterpret_cast<const float4*>(
-                src + (size_t)(r0 + rr) * F + c0);
-        float* d = dst + rr * STRIDE + c0;
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-}
-
-// acc_tile(LDS RT×STRIDE) += src_tile · W (or Wᵀ) — mfma 16×16×4
-DEV_INLINE void gemm_tile(const float* __restrict__ src, float* __restrict__
-                          dst, const float* __restrict__ W, bool transposeW,
-                          int tid) {
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int nw = blockDim.x >> 6;
-    const int r_in = lane & 15;
-    const int k_in = lane >> 4;
-    for (int t = wid; t < (RT / 16) * 2; t += nw) {
-        const int mt = t >> 1;
-        const int c0 = (t & 1) * 16;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < F / 4; ++kk) {
-            const int k = kk * 4 + k_in;
-            const float a = src[(mt * 16 + r_in) * STRIDE + k];
-            const float b = transposeW ? W[(c0 + r_in) * F + k]
-                                       : W[k * F + c0 + r_in];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            dst[(mt * 16 + (lane >> 4) * 4 + r) * STRIDE + c0 +
-                (lane & 15)] += acc[r];
-    }
-}
-
-// dW[i][j] += sum over the tile's rows of src[r][i]*delta[r][j] (atomics)
-DEV_INLINE void wgrad_tile(const float* __restrict__ src,
-                           const float* __restrict__ delta,
-                           float* __restrict__ dw_out, int tid) {
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int nw = blockDim.x >> 6;
-    const int k_in = lane >> 4;
-    const int c_in = lane & 15;
-    for (int t = wid; t < 4; t += nw) {
-        const int i0 = (t >> 1) * 16, j0 = (t & 1) * 16;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int kk = 0; kk < RT / 4; ++kk) {
-            const int r = kk * 4 + k_in;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                src[r * STRIDE + i0 + c_in], delta[r * STRIDE + j0 + c_in],
-                acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            atomicAdd(&dw_out[(i0 + (lane >> 4) * 4 + r) * F + j0
-                              + (lane & 15)], acc[r]);
     }
 }
 
@@ -138,26 +64,19 @@ __global__ void cheb_large_fwd_layer(
     for (int i = tid; i < K * F * F; i += nt) Wl[i] = W[i];
     for (int i = tid; i < F; i += nt) bl[i] = bias[i];
     for (int i = tid; i < RT * STRIDE; i += nt) Yt[i] = 0.f;
-    load_tile(xb, Xt, r0, Ee, tid, nt);
+    load_rows(Xt, xb, r0, RT, Ee, tid, nt);
     if (K > 1) spmv_tile(xb, Tt, ipt, cls, r0, Ee, tid, nt);
     __syncthreads();
-    gemm_tile(Xt, Yt, Wl, false, tid);
-    if (K > 1) gemm_tile(Tt, Yt, Wl + F * F, false, tid);
+    gemm_rows(Xt, Yt, Wl, false, RT, tid);
+    if (K > 1) gemm_rows(Tt, Yt, Wl + F * F, false, RT, tid);
     __syncthreads();
-    float* out = x_next + (size_t)b * x_stride;
-    for (int task = tid; task < RT * (F / 4); task += nt) {
-        const int rr = task >> 3;
-        const int c0 = (task & 7) * 4;
-        if (r0 + rr >= Ee) continue;
-        float4 v;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float y = Yt[rr * STRIDE + c0 + q] + bl[c0 + q];
-            y = last ? (y > 0.f ? y : 0.f) : (y > 0.f ? y : 0.2f * y);
-            (&v.x)[q] = y;
-        }
-        *reinterpret_cast<float4*>(out + (size_t)(r0 + rr) * F + c0) = v;
-    }
+    store_rows(Yt, x_next + (size_t)b * x_stride, r0, RT, Ee, tid, nt,
+               [&](float4 y, int c0) {
+                   return float4{act(y.x + bl[c0], last),
+                                 act(y.y + bl[c0 + 1], last),
+                                 act(y.z + bl[c0 + 2], last),
+                                 act(y.w + bl[c0 + 3], last)};
+               });
 }
 
 // ---- backward stage A (per layer): δpre = δ⊙act'(acts[l+1]);
@@ -192,41 +111,25 @@ __global__ void cheb_large_bwd_a(
     for (int i = tid; i < K * F * F; i += nt) Wl[i] = W[i];
     // δpre tile (mask applied on load)
     const float slope = last ? 0.f : 0.2f;
-    for (int task = tid; task < RT * (F / 4); task += nt) {
-        const int rr = task >> 3;
-        const int c0 = (task & 7) * 4;
-        float4 d = {0.f, 0.f, 0.f, 0.f};
-        if (r0 + rr < Ee) {
-            d = *reinterpret_cast<const float4*>(
-                del + (size_t)(r0 + rr) * F + c0);
-            const float4 a = *reinterpret_cast<const float4*>(
-                xa + (size_t)(r0 + rr) * F + c0);
-            d.x *= a.x > 0.f ? 1.f : slope;
-            d.y *= a.y > 0.f ? 1.f : slope;
-            d.z *= a.z > 0.f ? 1.f : slope;
-            d.w *= a.w > 0.f ? 1.f : slope;
-        }
-        float* t = Dt + rr * STRIDE + c0;
-        t[0] = d.x; t[1] = d.y; t[2] = d.z; t[3] = d.w;
-    }
-    load_tile(xl, Xt, r0, Ee, tid, nt);
+    load_rows(Dt, del, r0, RT, Ee, tid, nt, [&](float4 d, size_t off) {
+        const float4 a = *reinterpret_cast<const float4*>(xa + off);
+        d.x *= dact(a.x, slope);
+        d.y *= dact(a.y, slope);
+        d.z *= dact(a.z, slope);
+        d.w *= dact(a.w, slope);
+        return d;
+    });
+    load_rows(Xt, xl, r0, RT, Ee, tid, nt);
     __syncthreads();
 
-    // db partials (column sums of the tile)
-    {
-        const int nchunk = nt / F;
-        const int j = tid % F, ch = tid / F;
-        float acc = 0.f;
-        for (int rr = ch; rr < RT; rr += nchunk)
-            acc += Dt[rr * STRIDE + j];
-        atomicAdd(&db[(size_t)b * db_stride + j], acc);
-    }
-    wgrad_tile(Xt, Dt, dW + (size_t)b * dw_stride, tid);
+    // db partials (column sums of the tile; rows past Ee are zero)
+    db_colsum(Dt, RT, db + (size_t)b * db_stride, tid, nt);
+    wgrad_rows<1>(Xt, Dt, dW + (size_t)b * dw_stride, RT, tid);
     if (K > 1) {
         __syncthreads();
         spmv_tile(xl, Ot, ipt, cls, r0, Ee, tid, nt);   // T1 tile
         __syncthreads();
-        wgrad_tile(Ot, Dt, dW + (size_t)b * dw_stride + F * F, tid);
+        wgrad_rows<1>(Ot, Dt, dW + (size_t)b * dw_stride + F * F, RT, tid);
     }
     if (!want_dx) return;
     __syncthreads();
@@ -235,30 +138,15 @@ __global__ void cheb_large_bwd_a(
     if (K > 1) {
         for (int i = tid; i < RT * STRIDE; i += nt) Ot[i] = 0.f;
         __syncthreads();
-        gemm_tile(Dt, Ot, Wl + F * F, true, tid);
+        gemm_rows(Dt, Ot, Wl + F * F, true, RT, tid);
         __syncthreads();
-        float* ub = U + (size_t)b * Ee * F;
-        for (int task = tid; task < RT * (F / 4); task += nt) {
-            const int rr = task >> 3;
-            const int c0 = (task & 7) * 4;
-            if (r0 + rr >= Ee) continue;
-            float4 v = {Ot[rr * STRIDE + c0], Ot[rr * STRIDE + c0 + 1],
-                        Ot[rr * STRIDE + c0 + 2], Ot[rr * STRIDE + c0 + 3]};
-            *reinterpret_cast<float4*>(ub + (size_t)(r0 + rr) * F + c0) = v;
-        }
+        store_rows(Ot, U + (size_t)b * Ee * F, r0, RT, Ee, tid, nt);
     }
     for (int i = tid; i < RT * STRIDE; i += nt) Xt[i] = 0.f;  // reuse as acc
     __syncthreads();
-    gemm_tile(Dt, Xt, Wl, true, tid);
+    gemm_rows(Dt, Xt, Wl, true, RT, tid);
     __syncthreads();
-    for (int task = tid; task < RT * (F / 4); task += nt) {
-        const int rr = task >> 3;
-        const int c0 = (task & 7) * 4;
-        if (r0 + rr >= Ee) continue;
-        float4 v = {Xt[rr * STRIDE + c0], Xt[rr * STRIDE + c0 + 1],
-                    Xt[rr * STRIDE + c0 + 2], Xt[rr * STRIDE + c0 + 3]};
-        *reinterpret_cast<float4*>(del + (size_t)(r0 + rr) * F + c0) = v;
-    }
+    store_rows(Xt, del, r0, RT, Ee, tid, nt);
 }
 
 // ---- backward stage B (per layer): delta += A·U --------------------------
@@ -278,12 +166,7 @@ __global__ void cheb_large_bwd_b(
         const int c0 = (task & 7) * 4;
         const int r = r0 + rr;
         if (r >= Ee) continue;
-        float4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int a = ipt[r]; a < ipt[r + 1]; ++a) {
-            const float4 v = *reinterpret_cast<const float4*>(
-                ub + (size_t)cls[a] * F + c0);
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
+        const float4 acc = csr_gather4(ub, ipt, cls, r, c0);
         float* d = del + (size_t)r * F + c0;
         d[0] += acc.x; d[1] += acc.y; d[2] += acc.z; d[3] += acc.w;
     }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Stage ablation of cheb_bwd (timing only — masked outputs are wrong):
 times the kernel with cumulative stage masks and differences them.
-bit0 act-mask+db, bit1 load_acts+wgrads, bit2 dx gemm, bit3 spmv.
+bit0 act-mask+db, bit1 load_rows+wgrads, bit2 dx gemm, bit3 spmv.
 
 Run on MI355X:  python profiles/ablate_cheb_bwd.py
 """
@@ -34,6 +34,7 @@ def main():
     from multihop_offload_amd.harness.train_batched import \
         build_training_cases
     from multihop_offload_amd.ops import dispatch
+    from multihop_offload_amd.ops.functions import pack_cheb_params
 
     cases = build_training_cases(110, 1024, 16, 1000, 7, workers=8)
     model = ChebConvStack(K=2, dtype=torch.float32, seed=3)
@@ -50,12 +51,7 @@ def main():
     for layer in eng.model.layers:
         params += [layer.weight, layer.bias]
     x = torch.randn(eng.B, eng.Ee, 4, device="cuda")
-    Wp = x.new_zeros(5, 2, 32, 32)
-    bp = x.new_zeros(5, 32)
-    for l in range(5):
-        w, b = params[2 * l], params[2 * l + 1]
-        Wp[l, :w.shape[0], :w.shape[1], :w.shape[2]] = w
-        bp[l, :b.shape[0]] = b
+    Wp, bp = pack_cheb_params(params)
     lam, acts, t1s = ext.cheb_fwd(x, Wp, bp, eng.k_ext_indptr,
                                   eng.k_ext_base, eng.k_ext_cols,
                                   eng.k_ext_max_nnz)

@@ -72,13 +72,9 @@ def bench_config(name, nodes, batch, gtype, distinct, reps):
 
     from multihop_offload_amd.ops import dispatch
     ext = dispatch.require_hip()
-    Wp = x.new_zeros(5, 2, 32, 32)
-    bp = x.new_zeros(5, 32)
-    for l in range(5):
-        w, b = params[2 * l], params[2 * l + 1]
-        Wp[l, :w.shape[0], :w.shape[1], :w.shape[2]] = w
-        bp[l, :b.shape[0]] = b
-    from multihop_offload_amd.ops.functions import cheb_lds_fits
+    from multihop_offload_amd.ops.functions import (cheb_lds_fits,
+                                                    pack_cheb_params)
+    Wp, bp = pack_cheb_params(params)
     small = cheb_lds_fits(eng.Ee, 2)
     if small:
         out["cheb_fwd"] = timeit(lambda: ext.cheb_fwd(

@@ -2,12 +2,28 @@
 
     PYTORCH_ROCM_ARCH=gfx950 python setup.py build_ext --inplace
 """
+import glob
 import os
 
 from setuptools import setup
 from torch.utils.cpp_extension import BuildExtension, CUDAExtension
 
 os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
+
+
+class BuildExt(BuildExtension):
+    """``depends`` makes a header edit re-enter the build, but torch's ninja
+    rules record no header dependencies for .hip sources and would re-link
+    the stale objects: drop the objects older than a header first."""
+
+    def build_extension(self, ext):
+        newest = max(os.path.getmtime(d) for d in ext.depends)
+        for obj in glob.glob(os.path.join(self.build_temp, "**", "*.o"),
+                             recursive=True):
+            if os.path.getmtime(obj) < newest:
+                os.remove(obj)
+        super().build_extension(ext)
+
 
 setup(
     name="multihop_offload_amd",
@@ -25,11 +41,12 @@ setup(
                 "multihop_offload_amd/ops/hip/optimizer.hip",
                 "multihop_offload_amd/ops/hip/chebconv_large.hip",
             ],
+            depends=["multihop_offload_amd/ops/hip/cheb_tiles.h"],
             extra_compile_args={
                 "cxx": ["-O3"],
                 "nvcc": ["-O3"],
             },
         )
     ],
-    cmdclass={"build_ext": BuildExtension},
+    cmdclass={"build_ext": BuildExt},
 )

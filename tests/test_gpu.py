@@ -725,3 +725,147 @@ def test_train_batched_capture_smoke(tmp_path):
         "--guard_every", "0", "--capture",
         "--model_root", str(tmp_path), "--training_set", "CAPT"])
     assert any("tau" in h for h in hist)
+
+
+def _cheb_family_case(n, K):
+    """Seeded dense inputs on the support CSR of ``_cases(n, B=3)`` plus the
+    fp64 oracle (dense per-graph adjacency, the Chebyshev recurrence of
+    models/chebconv.py, dW/db from autograd)."""
+    from multihop_offload_amd.engine import EpisodeEngine
+    from multihop_offload_amd.models.chebconv import ChebConvStack
+
+    L, F = 5, 32
+    eng = EpisodeEngine(_cases(n, B=3), ChebConvStack(K=2, dtype=torch.float32,
+                                                      seed=0),
+                        device="cuda", dtype=torch.float32)
+    B, Ee = eng.B, eng.Ee
+    ipt = eng.k_ext_indptr.cpu().numpy()
+    base = eng.k_ext_base.cpu().numpy()
+    cols = eng.k_ext_cols.cpu().numpy()
+    A = torch.zeros(B, Ee, Ee, dtype=torch.float64)
+    for b in range(B):
+        for r in range(Ee):
+            for a in range(ipt[b, r], ipt[b, r + 1]):
+                A[b, r, cols[base[b] + a]] += 1.0
+    # the backward kernels propagate dX through A, not Aᵀ
+    assert torch.equal(A, A.transpose(1, 2))
+
+    # Weight scale: W_k ~ N(0, s_k²) with s_k = 2 / (K·sqrt(32)·‖T_k(A)‖₂),
+    # the spectral norm of the Chebyshev term taken over the batch from the
+    # eigenvalues of A.  A 32×32 Gaussian matrix of std s has norm about
+    # 2·s·sqrt(32), so each of the K terms T_k(A)·X·W_k of a layer has gain
+    # at most about 4/K and typically well below it; the fp64 activations
+    # stay O(1) through the five layers (asserted below).  b ~ N(0, 0.1²).
+    dmax = float(A.sum(dim=2).max())
+    ev = torch.linalg.eigvalsh(A)
+    tk = [torch.ones_like(ev), ev]
+    for k in range(2, K):
+        tk.append(2.0 * ev * tk[-1] - tk[-2])
+    gen = torch.Generator()
+    gen.manual_seed(1000 * n + K)
+    x = torch.randn(B, Ee, 4, generator=gen)
+    dlam = torch.randn(B, Ee, generator=gen)
+    W = torch.randn(L, K, F, F, generator=gen)
+    for k in range(K):
+        W[:, k] *= 2.0 / (K * F ** 0.5 * float(tk[k].abs().max()))
+    bias = 0.1 * torch.randn(L, F, generator=gen)
+
+    Wd = W.double().unsqueeze(0).repeat(B, 1, 1, 1, 1).requires_grad_()
+    bd = bias.double().unsqueeze(0).repeat(B, 1, 1).requires_grad_()
+    h = torch.zeros(B, Ee, F, dtype=torch.float64)
+    h[:, :, :4] = x.double()
+    acts = [h]
+    for l in range(L):
+        out = h @ Wd[:, l, 0]
+        t_prev, t_cur = h, A @ h
+        out = out + t_cur @ Wd[:, l, 1]
+        for k in range(2, K):
+            t_prev, t_cur = t_cur, 2.0 * (A @ t_cur) - t_prev
+            out = out + t_cur @ Wd[:, l, k]
+        out = out + bd[:, l].unsqueeze(1)
+        h = (torch.relu(out) if l == L - 1
+             else torch.nn.functional.leaky_relu(out, 0.2))
+        acts.append(h)
+    lam = h[:, :, 0]
+    (lam * dlam.double()).sum().backward()
+    for a in acts[1:]:
+        assert 0.1 < float(a.detach().abs().max()) < 10.0
+    want = dict(lam=lam.detach(), acts=torch.stack(acts, 1).detach(),
+                dW=Wd.grad, db=bd.grad)
+    return eng, x.cuda(), dlam.cuda(), W.cuda(), bias.cuda(), dmax, want
+
+
+@needs_gpu
+@pytest.mark.parametrize("n,K", [(20, 2), (30, 2), (20, 3)])
+def test_cheb_kernel_families_agree(n, K):
+    """The LDS-resident K<=2 kernels, the row-tiled large-graph kernels and
+    the generic-K kernels, called directly on the same dense inputs, all
+    match one fp64 oracle.  n=20: Ee=55 (rows_pad 64 with 9 padded rows,
+    one partial 64-row tile); n=30: Ee=85 (rows_pad 96: 12 GEMM tiles over
+    8 waves, 12 k-steps per wgrad half, two row tiles with the second
+    partial).  K=3 runs the recurrence path, which only the generic-K
+    kernels have."""
+    from multihop_offload_amd.ops import dispatch
+    ext = dispatch.require_hip()
+    eng, x, dlam, W, bias, dmax, want = _cheb_family_case(n, K)
+    assert eng.Ee == {20: 55, 30: 85}[n]
+    assert ext.cheb_fits_lds(eng.Ee, K)
+    csr = (eng.k_ext_indptr, eng.k_ext_base, eng.k_ext_cols)
+    nnz = eng.k_ext_max_nnz
+
+    got = {}
+    if K <= 2:
+        lam, acts, t1s = ext.cheb_fwd(x, W, bias, *csr, nnz)
+        got["cheb"] = (lam, acts) + tuple(
+            ext.cheb_bwd(dlam, acts, t1s, W, *csr, nnz))
+        lam, acts = ext.cheb_large_fwd(x, W, bias, *csr)
+        got["cheb_large"] = (lam, acts) + tuple(
+            ext.cheb_large_bwd(dlam, acts, W, *csr))
+    lam, acts, tks = ext.cheb_kn_fwd(x, W, bias, *csr, nnz)
+    got["cheb_kn"] = (lam, acts) + tuple(
+        ext.cheb_kn_bwd(dlam, acts, tks, W, *csr, nnz))
+
+    # Forward: rtol 1e-3, plus the absolute rounding floor of fp32 for
+    # elements that cancel towards zero: an activation is a K·32-term dot
+    # product over (up to dmax)-term neighbour sums, five layers deep, each
+    # addend carrying 2^-24 relative rounding of O(max|activation|) values.
+    amax = float(want["acts"].abs().max())
+    atol = 5 * (K * 32 + dmax) * 2.0 ** -24 * amax
+    for fam, (lam, acts, dW, db) in got.items():
+        for name, g, w in (("lam", lam, want["lam"]),
+                           ("acts", acts, want["acts"])):
+            g = g.double().cpu()
+            err = (g - w).abs()
+            print(f"{fam} n={n} K={K} {name}: max abs err "
+                  f"{float(err.max()):.3e} (atol {atol:.3e}), max rel err "
+                  f"{float((err / w.abs().clamp(min=atol)).max()):.3e}")
+            assert bool((err <= atol + 1e-3 * w.abs()).all()), (fam, name)
+        # gradients: per graph and layer, max-abs error below 5e-3 of the
+        # oracle's max-abs
+        for name, g, w in (("dW", dW, want["dW"]), ("db", db, want["db"])):
+            g = g.double().cpu()
+            assert g.shape == w.shape
+            worst = 0.0
+            for b in range(g.shape[0]):
+                for l in range(g.shape[1]):
+                    denom = float(w[b, l].abs().max())
+                    assert denom > 0
+                    worst = max(worst, float((g[b, l] - w[b, l]).abs().max())
+                                / denom)
+            print(f"{fam} n={n} K={K} {name}: worst max-abs err / max-abs "
+                  f"{worst:.3e}")
+            assert worst < 5e-3, (fam, name, worst)
+
+
+@needs_gpu
+def test_cheb_fits_lds_switch_point():
+    """The extension's fit decision (from the LDS plan that sizes the
+    launches) switches between the LDS-resident and the row-tiled path at
+    the same Ee as the closed form it replaced.  No kernel is launched."""
+    from multihop_offload_amd.ops import dispatch
+    ext = dispatch.require_hip()
+    for K in range(1, 7):
+        for Ee in range(1, 601):
+            rows_pad = (Ee + 15) & ~15
+            want = (3 * rows_pad * 33 + K * 1024 + 32) * 4 <= 160 * 1024
+            assert ext.cheb_fits_lds(Ee, K) == want, (Ee, K)
