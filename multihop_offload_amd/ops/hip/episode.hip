@@ -242,6 +242,10 @@ __global__ void walk_eval_kernel(
                 const float v = spb[(size_t)nb2 * N + d];
                 if (v < bestv) { bestv = v; bestn = nb2; bestl = alk[a]; }
             }
+            // precondition: a walked node has a neighbour with finite sp
+            // to d (connected graphs).  If none has, stop instead of
+            // indexing with -1; the walk is counted as truncated below.
+            if (bestl < 0) break;
             route_links[((size_t)b * J + j) * H + h] = bestl;
             atomicAdd(&lam[bestl], add);
             node = bestn;
