@@ -339,18 +339,19 @@ class EpisodeEngine:
         import os
         self.use_hip = (self.device.type == "cuda"
                         and os.environ.get("MHO_FORCE_TORCH") != "1")
-        # per-kernel LDS fit (large graphs fall back to the torch tensor
-        # path for that stage; the rest stay on the fused kernels)
-        LDS = 160 * 1024
-        self.hip_walk_ok = (3 * E + N) * 4 <= LDS
-        # the critic/actor kernels switch to global scratch for large
-        # graphs; these are the limits of that mode
-        self.hip_critic_ok = (2 * Ee + 3 * E) * 4 <= LDS
-        self.hip_actor_ok = 5 * E * 4 <= LDS
+        # per-kernel LDS fit, asked of the launchers' own plans (a stage
+        # whose kernel does not fit even in its global-scratch mode falls
+        # back to the torch tensor path; the rest stay on the fused
+        # kernels).  Every use is behind `use_hip and`.
+        self.hip_walk_ok = self.hip_critic_ok = self.hip_actor_ok = False
         if self.use_hip:
             assert dtype == torch.float32, "HIP kernels are fp32"
             from .ops import dispatch
-            dispatch.require_hip()
+            plan = dispatch.require_hip().queue_lds_plan(N, E, Ee, fp_iters)
+            self.hip_walk_ok = plan["walk_eval"]["fits"]
+            self.hip_critic_ok = plan["critic"]["fits"]
+            self.hip_actor_ok = (plan["actor_head_fwd"]["fits"]
+                                 and plan["actor_head_bwd"]["fits"])
 
     def set_rng_seed(self, seed: int):
         """Seed the in-kernel stateless sampler (per-DP-rank seeds keep the

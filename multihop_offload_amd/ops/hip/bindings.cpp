@@ -37,6 +37,7 @@ torch::Tensor actor_head_bwd_hip(
     torch::Tensor conf_cols, torch::Tensor rates, torch::Tensor bw_comp,
     torch::Tensor edges, torch::Tensor node_vedge, torch::Tensor T_arr,
     torch::Tensor E_arr, long iters, double cap);
+py::dict queue_lds_plan(long N, long E, long Ee, long iters);
 
 std::vector<torch::Tensor> cheb_fwd_hip(
     torch::Tensor x, torch::Tensor W, torch::Tensor bias,
@@ -81,6 +82,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("critic", &critic_hip);
     m.def("actor_head_fwd", &actor_head_fwd_hip);
     m.def("actor_head_bwd", &actor_head_bwd_hip);
+    m.def("queue_lds_plan", &queue_lds_plan);
     m.def("cheb_fwd", &cheb_fwd_hip);
     m.def("cheb_bwd", &cheb_bwd_hip);
     m.def("cheb_bwd_ablate", &cheb_bwd_hip_mask);

@@ -13,9 +13,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstddef>
-
-#define DEV_INLINE __device__ __forceinline__
+#include "gfx950.h"
 
 namespace cheb {
 
@@ -203,8 +201,6 @@ DEV_INLINE float4 csr_gather4(const float* __restrict__ src,
 // `nbuf` row buffers of rows_pad×STRIDE, K weight matrices, optionally the
 // bias row, and — when it still fits — the graph's CSR (Ee+1 row pointers +
 // max_nnz columns) so the SpMVs read it from LDS.
-constexpr size_t LDS_LIMIT = 160 * 1024;   // gfx950: 160 KiB per workgroup
-
 struct LdsPlan {
     int rows_pad;        // Ee rounded up to the 16-row MFMA tile
     size_t lds_bytes;    // dynamic LDS to launch with (CSR included if staged)

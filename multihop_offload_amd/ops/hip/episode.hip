@@ -17,9 +17,9 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
-namespace {
+#include "queue_model.h"
 
-#define DEV_INLINE __device__ __forceinline__
+namespace {
 
 DEV_INLINE float fmax1(float a, float b) { return a > b ? a : b; }
 
@@ -35,6 +35,23 @@ DEV_INLINE unsigned long long mix64(unsigned long long z) {
 DEV_INLINE float u01(unsigned long long h) {
     // top 24 bits → [0,1) float
     return (float)(h >> 40) * (1.0f / 16777216.0f);
+}
+
+// cost of offloading a job to server node sv: uplink + downlink along the
+// shortest path (floored at the hop count) + compute; sp_row/hop_row are
+// the rows of the job's source
+DEV_INLINE float server_cost(const float* sp_row, const float* hop_row,
+                             const float* uds, int sv, float ulj,
+                             float dlj) {
+    const float spv = sp_row[sv];
+    const float hpv = hop_row[sv];
+    return fmax1(spv * ulj, hpv) + fmax1(spv * dlj, hpv)
+           + fmax1(uds[sv] * ulj, 1.0f);
+}
+
+// unnormalised softmax weight of a cost; a non-finite cost weighs nothing
+DEV_INLINE float softmax_w(float c, float cmax) {
+    return isfinite(c) ? __expf((c < 1e30f ? c : 1e30f) - cmax) : 0.f;
 }
 
 // ---------------------------------------------------------------------------
@@ -73,19 +90,20 @@ __global__ void decide_kernel(
         if (!mask[bj]) { dst_out[bj] = s0; islocal_out[bj] = true; continue; }
         const float ulj = ul[bj], dlj = dl[bj];
         const float local = udsb[s0] * ulj;
+        const float* sp_row = spb + (size_t)s0 * N;
+        const float* hop_row = hpb + (size_t)s0 * N;
         int best_s;
         if (prob) {
             // softmax over raw costs (the reference's prob mode quirk:
             // HIGH-cost servers get HIGH probability — util.py:113-116);
-            // two passes: max, then inverse-CDF walk with one uniform
+            // three passes that each recompute the cost instead of storing
+            // S of them per thread: max, sum, then inverse-CDF walk with one
+            // uniform
             float cmax = local < 1e30f ? local : 1e30f;
             for (int s = 0; s < S; ++s) {
                 const int sv = srvb[s];
                 if (sv < 0) continue;
-                const float spv = spb[(size_t)s0 * N + sv];
-                const float hpv = hpb[(size_t)s0 * N + sv];
-                float c = fmax1(spv * ulj, hpv) + fmax1(spv * dlj, hpv)
-                          + fmax1(udsb[sv] * ulj, 1.0f);
+                float c = server_cost(sp_row, hop_row, udsb, sv, ulj, dlj);
                 if (isfinite(c)) { c = c < 1e30f ? c : 1e30f;
                                    cmax = c > cmax ? c : cmax; }
             }
@@ -93,28 +111,18 @@ __global__ void decide_kernel(
             for (int s = 0; s < S; ++s) {
                 const int sv = srvb[s];
                 if (sv < 0) continue;
-                const float spv = spb[(size_t)s0 * N + sv];
-                const float hpv = hpb[(size_t)s0 * N + sv];
-                float c = fmax1(spv * ulj, hpv) + fmax1(spv * dlj, hpv)
-                          + fmax1(udsb[sv] * ulj, 1.0f);
-                psum += isfinite(c) ? __expf((c < 1e30f ? c : 1e30f) - cmax)
-                                    : 0.f;
+                psum += softmax_w(
+                    server_cost(sp_row, hop_row, udsb, sv, ulj, dlj), cmax);
             }
-            const float ploc = isfinite(local)
-                ? __expf((local < 1e30f ? local : 1e30f) - cmax) : 0.f;
-            psum += ploc;
+            psum += softmax_w(local, cmax);
             const float r = u01(mix64(key ^ (unsigned long long)bj)) * psum;
             float acc = 0.f;
             best_s = -1;                     // fallthrough: local
             for (int s = 0; s < S; ++s) {
                 const int sv = srvb[s];
                 if (sv < 0) continue;
-                const float spv = spb[(size_t)s0 * N + sv];
-                const float hpv = hpb[(size_t)s0 * N + sv];
-                float c = fmax1(spv * ulj, hpv) + fmax1(spv * dlj, hpv)
-                          + fmax1(udsb[sv] * ulj, 1.0f);
-                acc += isfinite(c) ? __expf((c < 1e30f ? c : 1e30f) - cmax)
-                                   : 0.f;
+                acc += softmax_w(
+                    server_cost(sp_row, hop_row, udsb, sv, ulj, dlj), cmax);
                 if (r < acc) { best_s = s; break; }
             }
         } else {
@@ -126,10 +134,8 @@ __global__ void decide_kernel(
             for (int s = 0; s < S; ++s) {
                 const int sv = srvb[s];
                 if (sv < 0) continue;
-                const float spv = spb[(size_t)s0 * N + sv];
-                const float hpv = hpb[(size_t)s0 * N + sv];
-                const float c = fmax1(spv * ulj, hpv) + fmax1(spv * dlj, hpv)
-                              + fmax1(udsb[sv] * ulj, 1.0f);
+                const float c =
+                    server_cost(sp_row, hop_row, udsb, sv, ulj, dlj);
                 if (c < best) { best = c; best_s = s; }
             }
             if (local < best) best_s = -1;      // -1 = local
@@ -151,7 +157,7 @@ __global__ void decide_kernel(
 // ---------------------------------------------------------------------------
 // walk_eval: greedy next-hop walk + load accumulation + contention fixed
 // point + per-job empirical delays (offloading_v3.py:441-550).
-// grid.x = B; one workgroup per graph; LDS: lam[E], mu[E], nb[E], sload[N].
+// grid.x = B; one workgroup per graph; LDS regions: qm::walk_plan.
 //
 // unit_mtx determinism: several jobs can traverse the same link (or share a
 // destination) with DIFFERENT per-job fallback units when congested; the
@@ -173,11 +179,7 @@ __global__ void walk_eval_kernel(
     const int* __restrict__ adj_indptr,  // (B,N+1)
     const int* __restrict__ adj_idx,     // (B,2E)
     const int* __restrict__ adj_link,    // (B,2E)
-    const int* __restrict__ conf_indptr, // (B,E+1) into conf_cols[conf_base]
-    const long* __restrict__ conf_base,  // (B+1)
-    const int* __restrict__ conf_cols,   // flat, local link ids
-    const float* __restrict__ rates,     // (B,E)
-    const float* __restrict__ bw,        // (B,N)
+    const qm::Tables t,                  // bw = per-node bw (B,N)
     const int* __restrict__ edges,       // (B,E,2)
     int* __restrict__ route_links,       // (B,J,H) out, -1 pad
     int* __restrict__ nhop,              // (B,J) out
@@ -186,15 +188,14 @@ __global__ void walk_eval_kernel(
     bool* __restrict__ written,          // (B,N,N) out (prezeroed)
     unsigned long long* __restrict__ upack,  // (B,N,N) scratch
     int* __restrict__ overflow,          // (B) out
-    const float* __restrict__ T_arr,     // (B)
-    const int* __restrict__ E_arr,       // (B) real link counts
     const int* __restrict__ n_arr,       // (B) real node counts (padding)
-    int N, int E, int J, int H, int fp_iters) {
+    const qm::WalkPlan p, int N, int E, int J, int H, int fp_iters) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* lam = reinterpret_cast<float*>(smem_raw);          // E
-    float* mu = lam + E;                                      // E
-    float* busy = mu + E;                                     // E
-    float* sload = busy + E;                                  // N
+    float* lds = reinterpret_cast<float*>(smem_raw);
+    float* lam = lds + p.lam;
+    float* mu = lds + p.mu;
+    float* busy = lds + p.busy;
+    float* sload = lds + p.sload;
 
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
@@ -203,15 +204,12 @@ __global__ void walk_eval_kernel(
     const int* aip = adj_indptr + (size_t)b * (N + 1);
     const int* aix = adj_idx + (size_t)b * 2 * E;
     const int* alk = adj_link + (size_t)b * 2 * E;
-    const float* ratesb = rates + (size_t)b * E;
-    const int* cip = conf_indptr + (size_t)b * (E + 1);
-    const int* ccols = conf_cols + conf_base[b];
-    const float T = T_arr[b];
+    const qm::Graph g = qm::graph_view(t, b);
     unsigned long long* upk = upack + (size_t)b * N * N;
     // per-graph effective sizes: padded link slots / inert pad nodes are
     // isolated and never touched by routes, so every E/N-length loop below
     // runs on the real extent only (ragged-E batches, pad_to mixed-N)
-    const int Eb = E_arr[b];
+    const int Eb = g.Eb;
     const int nb_ = n_arr[b];
 
     for (int e = tid; e < Eb; e += nt) lam[e] = 0.0f;
@@ -260,27 +258,11 @@ __global__ void walk_eval_kernel(
     __syncthreads();
 
     // ---- stage 2: contention fixed point (offloading_v3.py:500-506) ------
-    for (int e = tid; e < Eb; e += nt) {
-        const float deg = (float)(cip[e + 1] - cip[e]);
-        mu[e] = ratesb[e] / (deg + 1.0f);
-    }
-    __syncthreads();
-    for (int it = 0; it < fp_iters; ++it) {
-        for (int e = tid; e < Eb; e += nt) {
-            const float r = lam[e] / mu[e];
-            busy[e] = r < 0.f ? 0.f : (r > 1.f ? 1.f : r);
-        }
-        __syncthreads();
-        for (int e = tid; e < Eb; e += nt) {
-            float nbv = 0.0f;
-            for (int a = cip[e]; a < cip[e + 1]; ++a) nbv += busy[ccols[a]];
-            mu[e] = ratesb[e] / (1.0f + nbv);
-        }
-        __syncthreads();
-    }
+    // only the last iterate is needed: row stride 0 keeps no history
+    qm::fixed_point_fwd(lam, g.rates, g.cip, g.ccols, mu, busy, Eb, 0,
+                        fp_iters, tid, nt);
 
     // ---- stage 3: per-job empirical delays (offloading_v3.py:522-549) ----
-    const float* bwb = bw + (size_t)b * N;
     const int* edg = edges + (size_t)b * E * 2;
     for (int j = tid; j < J; j += nt) {
         const size_t bj = (size_t)b * J + j;
@@ -293,9 +275,7 @@ __global__ void walk_eval_kernel(
         for (int h = 0; h < nhop[bj]; ++h) {
             const int l = route_links[((size_t)b * J + j) * H + h];
             if (l < 0) break;
-            const float gap = mu[l] - lam[l];
-            const float unit = gap > 0.f ? 1.0f / gap
-                                         : T * lam[l] / (tot * mu[l]);
+            const float unit = qm::emp_unit(lam[l], mu[l], g.T, tot);
             const int u = edg[l * 2], v = edg[l * 2 + 1];
             const unsigned long long pk = jtag | (unsigned long long)
                 __float_as_uint(unit);
@@ -304,9 +284,7 @@ __global__ void walk_eval_kernel(
             acc += fmax1(ulj * unit, nh) + fmax1(dlj * unit, nh);
         }
         const int d = (int)dstv[bj];
-        const float sgap = bwb[d] - sload[d];
-        const float sunit = sgap > 0.f ? 1.0f / sgap
-                                       : T * sload[d] / (ulj * bwb[d]);
+        const float sunit = qm::emp_unit(sload[d], g.bw[d], g.T, ulj);
         atomicMax(&upk[(size_t)d * N + d],
                   jtag | (unsigned long long)__float_as_uint(sunit));
         acc += fmax1(ulj * sunit, 1.0f);
@@ -378,32 +356,26 @@ std::vector<torch::Tensor> walk_eval_hip(
     // zeroes its own slice — empty, not zeros)
     auto upack = torch::empty({B, N, N}, opts_f.dtype(torch::kInt64));
     auto overflow = torch::zeros({B}, opts_i.dtype(torch::kInt32));
-    const size_t lds = sizeof(float) * (3 * (size_t)E + N);
-    TORCH_CHECK(lds <= 160 * 1024, "graph too large for LDS walk_eval");
-    // large graphs ship few workgroups (one per graph): widen them so the
-    // E-length loops and the N*N unpack keep more lanes busy per CU
-    const int threads = (E >= 1500 || N >= 500) ? 1024 : 256;
+    const qm::WalkPlan p = qm::walk_plan(N, E);
+    TORCH_CHECK(p.fits, "graph too large for LDS walk_eval");
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(walk_eval_kernel, dim3(B), dim3(threads), lds,
-                       stream.stream(),
+    hipLaunchKernelGGL(walk_eval_kernel, dim3(B), dim3(p.threads),
+                       p.lds_bytes, stream.stream(),
                        sp.data_ptr<float>(), src.data_ptr<long>(),
                        dst.data_ptr<long>(), mask.data_ptr<bool>(),
                        rate.data_ptr<float>(), ul.data_ptr<float>(),
                        dl.data_ptr<float>(),
                        adj_indptr.data_ptr<int>(), adj_idx.data_ptr<int>(),
                        adj_link.data_ptr<int>(),
-                       conf_indptr.data_ptr<int>(),
-                       conf_base.data_ptr<long>(),
-                       conf_cols.data_ptr<int>(), rates.data_ptr<float>(),
-                       bw.data_ptr<float>(), edges.data_ptr<int>(),
+                       qm::tables(conf_indptr, conf_base, conf_cols, rates,
+                                  bw, T_arr, E_arr),
+                       edges.data_ptr<int>(),
                        route_links.data_ptr<int>(), nhop.data_ptr<int>(),
                        delay_emp.data_ptr<float>(),
                        unit_mtx.data_ptr<float>(), written.data_ptr<bool>(),
                        reinterpret_cast<unsigned long long*>(
                            upack.data_ptr<long>()),
-                       overflow.data_ptr<int>(),
-                       T_arr.data_ptr<float>(), E_arr.data_ptr<int>(),
-                       n_arr.data_ptr<int>(), N, E, J, (int)H,
+                       overflow.data_ptr<int>(), n_arr.data_ptr<int>(), p, N, E, J, (int)H,
                        (int)fp_iters);
     return {route_links, nhop, delay_emp, unit_mtx, written, overflow};
 }

@@ -18,7 +18,7 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
-#define LDS_BYTES (160 * 1024)
+#include "gfx950.h"
 
 namespace {
 
@@ -354,7 +354,7 @@ torch::Tensor floyd_warshall_hip(torch::Tensor w,
     AT_DISPATCH_FLOATING_TYPES(d.scalar_type(), "fw", [&] {
         const int Ns = sizeof(scalar_t) == 4 ? ((N + 3) & ~3) : N;
         const size_t lds = (size_t)N * Ns * sizeof(scalar_t);
-        if (lds <= LDS_BYTES) {
+        if (lds <= LDS_LIMIT) {
             hipLaunchKernelGGL(fw_lds_kernel<scalar_t>, dim3(B), dim3(512),
                                lds, stream.stream(),
                                d.data_ptr<scalar_t>(), N, np_);

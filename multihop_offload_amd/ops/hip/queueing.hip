@@ -10,6 +10,10 @@
 // actor_head_fwd/bwd — the actor delay head (:229-274): λ → fixed point →
 //   link/node delays → N×N delay matrix, and its VJP (grad_dist → δλ).
 //
+// The fixed point, the delay units and each kernel's LDS plan (regions,
+// launch size, LDS-resident or global-scratch "large" mode) are in
+// queue_model.h.
+//
 // Gradient conventions match torch autograd exactly (tests):
 //   clamp passes gradient at the boundaries inclusive;
 //   torch.maximum splits the gradient 0.5/0.5 at exact ties.
@@ -18,99 +22,14 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include "queue_model.h"
+
 namespace {
 
-#define DEV_INLINE __device__ __forceinline__
-
-// forward fixed point storing mu_t for t=0..iters into `hist` ((iters+1)*E)
-// Eb: real (per-graph) link count the loops run over; Estride: row stride
-// of the mu history (the BATCH-max E — ragged-E / padded batches)
-DEV_INLINE void fixed_point_fwd(const float* lam, const float* rates,
-                                const int* cip, const int* ccols,
-                                float* hist, float* busy, int Eb,
-                                int Estride, int iters, int tid, int nt) {
-    for (int e = tid; e < Eb; e += nt) {
-        const float deg = (float)(cip[e + 1] - cip[e]);
-        hist[e] = rates[e] / (deg + 1.0f);
-    }
-    __syncthreads();
-    for (int t = 1; t <= iters; ++t) {
-        const float* mu_prev = hist + (size_t)(t - 1) * Estride;
-        float* mu_cur = hist + (size_t)t * Estride;
-        for (int e = tid; e < Eb; e += nt) {
-            const float r = lam[e] / mu_prev[e];
-            busy[e] = r < 0.f ? 0.f : (r > 1.f ? 1.f : r);
-        }
-        __syncthreads();
-        for (int e = tid; e < Eb; e += nt) {
-            float nbv = 0.0f;
-            for (int a = cip[e]; a < cip[e + 1]; ++a) nbv += busy[ccols[a]];
-            mu_cur[e] = rates[e] / (1.0f + nbv);
-        }
-        __syncthreads();
-    }
-}
-
-// reverse through the unrolled fixed point: consumes dmu (cotangent on
-// mu_iters), accumulates into dlam.  Scratch: dnb[E], dbusy[E].
-DEV_INLINE void fixed_point_bwd(const float* lam, const float* rates,
-                                const int* cip, const int* ccols,
-                                const float* hist, float* dmu, float* dnb,
-                                float* dbusy, float* dlam, int Eb,
-                                int Estride, int iters, int tid, int nt) {
-    for (int t = iters; t >= 1; --t) {
-        const float* mu_prev = hist + (size_t)(t - 1) * Estride;
-        const float* mu_cur = hist + (size_t)t * Estride;
-        for (int e = tid; e < Eb; e += nt) {
-            // mu_t = rates/(1+nb) => d nb = -mu_t^2/rates * d mu_t
-            dnb[e] = -mu_cur[e] * mu_cur[e] / rates[e] * dmu[e];
-        }
-        __syncthreads();
-        for (int e = tid; e < Eb; e += nt) {
-            // busy feeds the nb of every conflicting link (A symmetric)
-            float acc = 0.0f;
-            for (int a = cip[e]; a < cip[e + 1]; ++a) acc += dnb[ccols[a]];
-            dbusy[e] = acc;
-        }
-        __syncthreads();
-        for (int e = tid; e < Eb; e += nt) {
-            const float ratio = lam[e] / mu_prev[e];
-            const float pass = (ratio <= 1.0f) ? 1.0f : 0.0f;  // ratio>=0
-            const float g = pass * dbusy[e];
-            dlam[e] += g / mu_prev[e];
-            dmu[e] = -g * lam[e] / (mu_prev[e] * mu_prev[e]);
-        }
-        __syncthreads();
-    }
-}
-
-// unit = 1/(mu-lam), overwritten by T*lam/(denom*mu) where lam-mu > 0.
-// cap > 0 clamps the 1/(mu-lam) branch (torch.clamp semantics: value
-// capped, gradient zero where inv > cap) — pole mitigation for training.
-DEV_INLINE float unit_fwd(float lam, float mu, float T, float denom,
-                          float cap) {
-    if ((lam - mu) > 0.f) return T * lam / (denom * mu);
-    const float inv = 1.0f / (mu - lam);
-    return (cap > 0.f && inv > cap) ? cap : inv;
-}
-// cotangents: given dunit, produce (dlam, dmu) contributions
-DEV_INLINE void unit_bwd(float lam, float mu, float T, float denom,
-                         float cap, float dunit, float* dlam, float* dmu) {
-    if ((lam - mu) > 0.f) {
-        *dlam = dunit * T / (denom * mu);
-        *dmu = -dunit * T * lam / (denom * mu * mu);
-    } else {
-        const float inv = 1.0f / (mu - lam);
-        if (cap > 0.f && inv > cap) { *dlam = 0.f; *dmu = 0.f; return; }
-        *dlam = dunit * inv * inv;
-        *dmu = -dunit * inv * inv;
-    }
-}
+using namespace qm;
 
 // ---------------------------------------------------------------------------
-// critic: loss + grad_edge in one pass.  LDS (floats):
-//   lam_e[Ee] | unit[Ee] | dunit[Ee] | dlam[Ee] | dgre[Ee]
-//   | hist[(iters+1)*E] | s1[E] | s2[E]
+// critic: loss + grad_edge in one pass.
 // ---------------------------------------------------------------------------
 __global__ void critic_kernel(
     const int* __restrict__ route_links,   // (B,J,H) -1 pad
@@ -120,62 +39,37 @@ __global__ void critic_kernel(
     const float* __restrict__ rate,        // (B,J)
     const float* __restrict__ ul,          // (B,J)
     const float* __restrict__ dl,          // (B,J)
-    const int* __restrict__ conf_indptr,   // (B,E+1)
-    const long* __restrict__ conf_base,    // (B+1)
-    const int* __restrict__ conf_cols,     // flat local
-    const float* __restrict__ rates,       // (B,E)
-    const float* __restrict__ bw_comp,     // (B,C)
-    const int* __restrict__ E_arr,         // (B) real link counts
-    float* __restrict__ grad_edge,         // (B,Ee) out (prezeroed)
+    const Tables t,                        // bw = bw_comp (B,C)
+    float* __restrict__ grad_edge,         // (B,Ee) out (large: prezeroed)
     float* __restrict__ loss_out,          // (B,) out
-    const float* __restrict__ T_arr,       // (B)
     float* __restrict__ g_hist,            // (B,(iters+1),E) scratch | null
     float* __restrict__ g_dunit,           // (B,Ee) scratch (prezeroed)
     float* __restrict__ g_dlam,            // (B,Ee) scratch (prezeroed)
-    int large,                             // 1: use global scratch
+    const CriticPlan p,
     float cap,                             // delay clamp (0 = off)
     int E, int C, int Ee, int J, int H, int iters) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int b_ = blockIdx.x;
-    float* lam_e = reinterpret_cast<float*>(smem_raw);
-    float* unit = lam_e + Ee;
-    float* dunit;
-    float* dlam;
-    float* dgre;
-    float* hist;
-    float* s1;
-    if (large) {
-        // large graphs (e.g. 1000-node ER): reverse-pass accumulators and
-        // the mu history live in global scratch (same-CU coherence through
-        // __syncthreads suffices — one workgroup per graph)
-        dunit = g_dunit + (size_t)b_ * Ee;
-        dlam = g_dlam + (size_t)b_ * Ee;
-        dgre = grad_edge + (size_t)b_ * Ee;   // accumulate output directly
-        hist = g_hist + (size_t)b_ * (iters + 1) * E;
-        s1 = unit + Ee;
-    } else {
-        dunit = unit + Ee;
-        dlam = dunit + Ee;
-        dgre = dlam + Ee;
-        hist = dgre + Ee;
-        s1 = hist + (size_t)(iters + 1) * E;
-    }
-    float* s2 = s1 + E;
-    float* s3 = s2 + E;
-    __shared__ float loss_acc;
-
+    float* lds = reinterpret_cast<float*>(smem_raw);
     const int b = blockIdx.x;
     const int tid = threadIdx.x, nt = blockDim.x;
-    const int* cip = conf_indptr + (size_t)b * (E + 1);
-    const int* ccols = conf_cols + conf_base[b];
-    const float* ratesb = rates + (size_t)b * E;
-    const float* bwb = bw_comp + (size_t)b * C;
-    const float T = T_arr[b];
-    const int Eb = E_arr[b];
+    // large graphs (e.g. 1000-node ER): reverse-pass accumulators and the mu
+    // history live in global scratch (same-CU coherence through
+    // __syncthreads suffices — one workgroup per graph)
+    float* lam_e = lds + p.lam_e;
+    float* unit = lds + p.unit;
+    float* dunit = region(lds, p.dunit, g_dunit + (size_t)b * Ee);
+    float* dlam = region(lds, p.dlam, g_dlam + (size_t)b * Ee);
+    float* dgre = region(lds, p.dgre, grad_edge + (size_t)b * Ee);
+    float* hist = region(lds, p.hist, g_hist + (size_t)b * (iters + 1) * E);
+    float* s1 = lds + p.s1;
+    float* s2 = lds + p.s2;
+    float* s3 = lds + p.s3;
+    __shared__ float loss_acc;
+    const Graph g = graph_view(t, b);
 
     for (int e = tid; e < Ee; e += nt) {
         lam_e[e] = 0.f;
-        if (!large) { dunit[e] = 0.f; dlam[e] = 0.f; dgre[e] = 0.f; }
+        if (!p.large) { dunit[e] = 0.f; dlam[e] = 0.f; dgre[e] = 0.f; }
         // (large mode: the global scratch arrives prezeroed)
     }
     if (tid == 0) loss_acc = 0.f;
@@ -197,13 +91,13 @@ __global__ void critic_kernel(
     __syncthreads();
 
     // ---- fixed point + unit delays ---------------------------------------
-    fixed_point_fwd(lam_e, ratesb, cip, ccols, hist, s1, Eb, E, iters,
+    fixed_point_fwd(lam_e, g.rates, g.cip, g.ccols, hist, s1, g.Eb, E, iters,
                     tid, nt);
     const float* mu_last = hist + (size_t)iters * E;
-    for (int e = tid; e < Eb; e += nt)
-        unit[e] = unit_fwd(lam_e[e], mu_last[e], T, 101.0f, cap);
+    for (int e = tid; e < g.Eb; e += nt)
+        unit[e] = unit_fwd(lam_e[e], mu_last[e], g.T, 101.0f, cap);
     for (int k = tid; k < C; k += nt)
-        unit[E + k] = unit_fwd(lam_e[E + k], bwb[k], T, 100.0f, cap);
+        unit[E + k] = unit_fwd(lam_e[E + k], g.bw[k], g.T, 100.0f, cap);
     __syncthreads();
 
     // ---- loss + dL/dunit over route entries ------------------------------
@@ -228,20 +122,22 @@ __global__ void critic_kernel(
     __syncthreads();
 
     // ---- reverse: dunit → (dlam over links via fixed point, direct nodes)
-    for (int e = tid; e < Eb; e += nt) {
+    for (int e = tid; e < g.Eb; e += nt) {
         float dl_, dm_;
-        unit_bwd(lam_e[e], mu_last[e], T, 101.0f, cap, dunit[e], &dl_, &dm_);
+        unit_bwd(lam_e[e], mu_last[e], g.T, 101.0f, cap, dunit[e], &dl_,
+                 &dm_);
         dlam[e] += dl_;
         s2[e] = dm_;                               // dmu into the reverse
     }
     for (int k = tid; k < C; k += nt) {
         float dl_, dm_;
-        unit_bwd(lam_e[E + k], bwb[k], T, 100.0f, cap, dunit[E + k], &dl_, &dm_);
+        unit_bwd(lam_e[E + k], g.bw[k], g.T, 100.0f, cap, dunit[E + k], &dl_,
+                 &dm_);
         dlam[E + k] += dl_;                        // bw is constant
     }
     __syncthreads();
-    fixed_point_bwd(lam_e, ratesb, cip, ccols, hist, s2 /*dmu*/, s1 /*dnb*/,
-                    s3 /*dbusy*/, dlam, Eb, E, iters, tid, nt);
+    fixed_point_bwd(lam_e, g.rates, g.cip, g.ccols, hist, s2 /*dmu*/,
+                    s1 /*dnb*/, s3 /*dbusy*/, dlam, g.Eb, E, iters, tid, nt);
     __syncthreads();
 
     // ---- grad_routes prefix scan → grad_edge -----------------------------
@@ -265,7 +161,7 @@ __global__ void critic_kernel(
         }
     }
     __syncthreads();
-    if (!large) {
+    if (!p.large) {
         float* geb = grad_edge + (size_t)b * Ee;
         for (int e = tid; e < Ee; e += nt) geb[e] = dgre[e];
     }
@@ -274,54 +170,38 @@ __global__ void critic_kernel(
 
 // ---------------------------------------------------------------------------
 // actor head forward: λ_ext → delays → (B,N,N) delay matrix; saves mu
-// history + λ for backward.  LDS: lam[E] | hist[(iters+1)*E] | busy[E]
+// history + λ for backward.
 // ---------------------------------------------------------------------------
 __global__ void actor_head_fwd_kernel(
     const float* __restrict__ lam_ext,     // (B,Ee)
-    const int* __restrict__ conf_indptr,
-    const long* __restrict__ conf_base,
-    const int* __restrict__ conf_cols,
-    const float* __restrict__ rates,       // (B,E)
-    const float* __restrict__ bw_comp,     // (B,C)
+    const Tables t,                        // bw = bw_comp (B,C)
     const int* __restrict__ edges,         // (B,E,2)
     const long* __restrict__ node_vedge,   // (B,N)
     float* __restrict__ dm,                // (B,N,N) out (prezeroed)
     float* __restrict__ mu_hist_out,       // (B,(iters+1),E) out
-    const float* __restrict__ T_arr,
-    const int* __restrict__ E_arr,         // (B) real link counts (ragged)
-    int large, float cap, int N, int E, int C, int Ee, int iters) {
+    const ActorFwdPlan p, float cap, int N, int E, int C, int Ee,
+    int iters) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* lam = reinterpret_cast<float*>(smem_raw);       // E
-    float* hist;
-    float* busy;
-    if (large) {
-        hist = mu_hist_out + (size_t)blockIdx.x * (iters + 1) * E;
-        busy = lam + E;
-    } else {
-        hist = lam + E;
-        busy = hist + (size_t)(iters + 1) * E;
-    }
-
+    float* lds = reinterpret_cast<float*>(smem_raw);
     const int b = blockIdx.x;
     const int tid = threadIdx.x, nt = blockDim.x;
+    float* ho = mu_hist_out + (size_t)b * (iters + 1) * E;
+    float* lam = lds + p.lam;
+    float* hist = region(lds, p.hist, ho);
+    float* busy = lds + p.busy;
+    const Graph g = graph_view(t, b);
     const float* le = lam_ext + (size_t)b * Ee;
-    const int* cip = conf_indptr + (size_t)b * (E + 1);
-    const int* ccols = conf_cols + conf_base[b];
-    const float* ratesb = rates + (size_t)b * E;
-    const float* bwb = bw_comp + (size_t)b * C;
     const int* edg = edges + (size_t)b * E * 2;
     const long* nv = node_vedge + (size_t)b * N;
     float* dmb = dm + (size_t)b * N * N;
-    const float T = T_arr[b];
 
-    const int Eb = E_arr[b];
-    for (int e = tid; e < Eb; e += nt) lam[e] = le[e];
+    for (int e = tid; e < g.Eb; e += nt) lam[e] = le[e];
     __syncthreads();
-    fixed_point_fwd(lam, ratesb, cip, ccols, hist, busy, Eb, E, iters,
+    fixed_point_fwd(lam, g.rates, g.cip, g.ccols, hist, busy, g.Eb, E, iters,
                     tid, nt);
     const float* mu_last = hist + (size_t)iters * E;
-    for (int e = tid; e < Eb; e += nt) {
-        const float d = unit_fwd(lam[e], mu_last[e], T, 101.0f, cap);
+    for (int e = tid; e < g.Eb; e += nt) {
+        const float d = unit_fwd(lam[e], mu_last[e], g.T, 101.0f, cap);
         const int u = edg[e * 2], v = edg[e * 2 + 1];
         dmb[(size_t)u * N + v] = d;
         dmb[(size_t)v * N + u] = d;
@@ -329,91 +209,73 @@ __global__ void actor_head_fwd_kernel(
     for (int n = tid; n < N; n += nt) {
         const long ve = nv[n];
         dmb[(size_t)n * N + n] =
-            ve >= 0 ? unit_fwd(le[ve], bwb[ve - E], T, 100.0f, cap) : INFINITY;
+            ve >= 0 ? unit_fwd(le[ve], g.bw[ve - E], g.T, 100.0f, cap)
+                    : INFINITY;
     }
-    if (!large) {
-        float* ho = mu_hist_out + (size_t)b * (iters + 1) * E;
+    if (!p.large) {
         for (size_t i = tid; i < (size_t)(iters + 1) * E; i += nt)
             ho[i] = hist[i];
     }
 }
 
 // actor head backward: grad_dist (B,N,N) → δλ_ext (B,Ee)
-// LDS: lam[E] | hist[(iters+1)*E] | dmu[E] | dlam[E] | s1[E] | s2[E]
 __global__ void actor_head_bwd_kernel(
     const float* __restrict__ grad_dist,   // (B,N,N)
     const float* __restrict__ lam_ext,     // (B,Ee)
     const float* __restrict__ mu_hist,     // (B,(iters+1),E)
-    const int* __restrict__ conf_indptr,
-    const long* __restrict__ conf_base,
-    const int* __restrict__ conf_cols,
-    const float* __restrict__ rates,
-    const float* __restrict__ bw_comp,
+    const Tables t,                        // bw = bw_comp (B,C)
     const int* __restrict__ edges,
     const long* __restrict__ node_vedge,
     float* __restrict__ dlam_ext,          // (B,Ee) out
-    const float* __restrict__ T_arr,
-    const int* __restrict__ E_arr,
-    int large, float cap, int N, int E, int C, int Ee, int iters) {
+    const ActorBwdPlan p, float cap, int N, int E, int C, int Ee,
+    int iters) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* lam = reinterpret_cast<float*>(smem_raw);
-    const float* hist;
-    float* dmu;
-    if (large) {
-        hist = mu_hist + (size_t)blockIdx.x * (iters + 1) * E;
-        dmu = lam + E;
-    } else {
-        float* h = lam + E;
-        hist = h;
-        dmu = h + (size_t)(iters + 1) * E;
-    }
-    float* dlam = dmu + E;
-    float* s1 = dlam + E;
-    float* s2 = s1 + E;
-
+    float* lds = reinterpret_cast<float*>(smem_raw);
     const int b = blockIdx.x;
     const int tid = threadIdx.x, nt = blockDim.x;
+    const float* hg = mu_hist + (size_t)b * (iters + 1) * E;
+    float* lam = lds + p.lam;
+    const float* hist = region(lds, p.hist, hg);
+    float* dmu = lds + p.dmu;
+    float* dlam = lds + p.dlam;
+    float* s1 = lds + p.s1;
+    float* s2 = lds + p.s2;
+    const Graph g = graph_view(t, b);
     const float* le = lam_ext + (size_t)b * Ee;
     const float* gd = grad_dist + (size_t)b * N * N;
-    const int* cip = conf_indptr + (size_t)b * (E + 1);
-    const int* ccols = conf_cols + conf_base[b];
-    const float* ratesb = rates + (size_t)b * E;
-    const float* bwb = bw_comp + (size_t)b * C;
     const int* edg = edges + (size_t)b * E * 2;
     const long* nv = node_vedge + (size_t)b * N;
     float* out = dlam_ext + (size_t)b * Ee;
-    const float T = T_arr[b];
 
-    const int Eb = E_arr[b];
-    for (int e = tid; e < Eb; e += nt) lam[e] = le[e];
-    if (!large) {
-        float* h = lam + E;
+    for (int e = tid; e < g.Eb; e += nt) lam[e] = le[e];
+    if (!p.large) {
+        float* h = lds + p.hist;
         for (size_t i = tid; i < (size_t)(iters + 1) * E; i += nt)
-            h[i] = mu_hist[(size_t)b * (iters + 1) * E + i];
+            h[i] = hg[i];
     }
     __syncthreads();
     const float* mu_last = hist + (size_t)iters * E;
 
     // link part: cotangent = gd[u,v] + gd[v,u] (dm wrote both)
-    for (int e = tid; e < Eb; e += nt) {
+    for (int e = tid; e < g.Eb; e += nt) {
         const int u = edg[e * 2], v = edg[e * 2 + 1];
         const float dd = gd[(size_t)u * N + v] + gd[(size_t)v * N + u];
         float dl_, dm_;
-        unit_bwd(lam[e], mu_last[e], T, 101.0f, cap, dd, &dl_, &dm_);
+        unit_bwd(lam[e], mu_last[e], g.T, 101.0f, cap, dd, &dl_, &dm_);
         dlam[e] = dl_;
         dmu[e] = dm_;
     }
     __syncthreads();
-    fixed_point_bwd(lam, ratesb, cip, ccols, hist, dmu, s1, s2, dlam,
-                    Eb, E, iters, tid, nt);
+    fixed_point_bwd(lam, g.rates, g.cip, g.ccols, hist, dmu, s1, s2, dlam,
+                    g.Eb, E, iters, tid, nt);
 
-    for (int e = tid; e < E; e += nt) out[e] = e < Eb ? dlam[e] : 0.f;
+    for (int e = tid; e < E; e += nt) out[e] = e < g.Eb ? dlam[e] : 0.f;
     // node part: diagonal cotangent, direct (no fixed point)
     for (int n = tid; n < N; n += nt) {
         const long ve = nv[n];
         if (ve >= 0) {
             float dl_, dm_;
-            unit_bwd(le[ve], bwb[ve - E], T, 100.0f, cap,
+            unit_bwd(le[ve], g.bw[ve - E], g.T, 100.0f, cap,
                      gd[(size_t)n * N + n], &dl_, &dm_);
             out[ve] = dl_;
         }
@@ -437,16 +299,11 @@ std::vector<torch::Tensor> critic_hip(
     const int H = route_links.size(2);
     const int E = rates.size(1), C = bw_comp.size(1);
     auto loss = torch::empty({B}, rates.options());
-    size_t lds = sizeof(float) *
-        (5 * (size_t)Ee + (size_t)(iters + 1) * E + 3 * (size_t)E);
-    int large = 0;
+    const CriticPlan p = critic_plan(E, (int)Ee, (int)iters);
+    TORCH_CHECK(p.fits, "graph too large even for the global-scratch critic");
     torch::Tensor g_hist, g_dunit, g_dlam;
     torch::Tensor grad_edge;
-    if (lds > 160 * 1024) {
-        large = 1;
-        lds = sizeof(float) * (2 * (size_t)Ee + 3 * (size_t)E);
-        TORCH_CHECK(lds <= 160 * 1024,
-                    "graph too large even for the global-scratch critic");
+    if (p.large) {
         g_hist = torch::empty({B, iters + 1, (long)E}, rates.options());
         g_dunit = torch::zeros({B, (long)Ee}, rates.options());
         g_dlam = torch::zeros({B, (long)Ee}, rates.options());
@@ -458,22 +315,18 @@ std::vector<torch::Tensor> critic_hip(
         // small mode copies the full dgre LDS row out — no prezero needed
         grad_edge = torch::empty({B, (long)Ee}, rates.options());
     }
-    const int threads = E >= 1500 ? 1024 : 256;
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(critic_kernel, dim3(B), dim3(threads), lds,
+    hipLaunchKernelGGL(critic_kernel, dim3(B), dim3(p.threads), p.lds_bytes,
                        stream.stream(),
                        route_links.data_ptr<int>(), nhop.data_ptr<int>(),
                        vedge_dst.data_ptr<long>(), mask.data_ptr<bool>(),
                        rate.data_ptr<float>(), ul.data_ptr<float>(),
                        dl.data_ptr<float>(),
-                       conf_indptr.data_ptr<int>(),
-                       conf_base.data_ptr<long>(),
-                       conf_cols.data_ptr<int>(), rates.data_ptr<float>(),
-                       bw_comp.data_ptr<float>(), E_arr.data_ptr<int>(),
+                       tables(conf_indptr, conf_base, conf_cols, rates,
+                              bw_comp, T_arr, E_arr),
                        grad_edge.data_ptr<float>(), loss.data_ptr<float>(),
-                       T_arr.data_ptr<float>(),
                        g_hist.data_ptr<float>(), g_dunit.data_ptr<float>(),
-                       g_dlam.data_ptr<float>(), large, (float)cap,
+                       g_dlam.data_ptr<float>(), p, (float)cap,
                        E, C, (int)Ee, J, H, (int)iters);
     return {grad_edge, loss};
 }
@@ -491,26 +344,17 @@ std::vector<torch::Tensor> actor_head_fwd_hip(
     // adj / `written` everywhere downstream — skip the fill launch
     auto dm = torch::empty({B, N, N}, lam_ext.options());
     auto mu_hist = torch::empty({B, iters + 1, (long)E}, lam_ext.options());
-    size_t lds = sizeof(float) * ((size_t)(iters + 2) * E + E);
-    int large = 0;
-    if (lds > 160 * 1024) {
-        large = 1;
-        lds = sizeof(float) * 2 * (size_t)E;
-    }
-    TORCH_CHECK(lds <= 160 * 1024, "graph too large for LDS actor head");
-    const int threads = E >= 1500 ? 1024 : 256;
+    const ActorFwdPlan p = actor_fwd_plan(E, (int)iters);
+    TORCH_CHECK(p.fits, "graph too large for LDS actor head");
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(actor_head_fwd_kernel, dim3(B), dim3(threads), lds,
-                       stream.stream(),
+    hipLaunchKernelGGL(actor_head_fwd_kernel, dim3(B), dim3(p.threads),
+                       p.lds_bytes, stream.stream(),
                        lam_ext.data_ptr<float>(),
-                       conf_indptr.data_ptr<int>(),
-                       conf_base.data_ptr<long>(),
-                       conf_cols.data_ptr<int>(), rates.data_ptr<float>(),
-                       bw_comp.data_ptr<float>(), edges.data_ptr<int>(),
-                       node_vedge.data_ptr<long>(), dm.data_ptr<float>(),
-                       mu_hist.data_ptr<float>(),
-                       T_arr.data_ptr<float>(), E_arr.data_ptr<int>(),
-                       large, (float)cap, (int)N, E, C, Ee, (int)iters);
+                       tables(conf_indptr, conf_base, conf_cols, rates,
+                              bw_comp, T_arr, E_arr),
+                       edges.data_ptr<int>(), node_vedge.data_ptr<long>(),
+                       dm.data_ptr<float>(), mu_hist.data_ptr<float>(),
+                       p, (float)cap, (int)N, E, C, Ee, (int)iters);
     return {dm, mu_hist};
 }
 
@@ -524,25 +368,33 @@ torch::Tensor actor_head_bwd_hip(
     const int E = rates.size(1), C = bw_comp.size(1);
     const int N = grad_dist.size(1);
     auto dlam = torch::zeros_like(lam_ext);
-    size_t lds = sizeof(float) * ((size_t)(iters + 1) * E + 5 * (size_t)E);
-    int large = 0;
-    if (lds > 160 * 1024) {
-        large = 1;
-        lds = sizeof(float) * 5 * (size_t)E;
-    }
-    TORCH_CHECK(lds <= 160 * 1024, "graph too large for LDS actor head bwd");
-    const int threads = E >= 1500 ? 1024 : 256;
+    const ActorBwdPlan p = actor_bwd_plan(E, (int)iters);
+    TORCH_CHECK(p.fits, "graph too large for LDS actor head bwd");
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(actor_head_bwd_kernel, dim3(B), dim3(threads), lds,
-                       stream.stream(),
+    hipLaunchKernelGGL(actor_head_bwd_kernel, dim3(B), dim3(p.threads),
+                       p.lds_bytes, stream.stream(),
                        grad_dist.data_ptr<float>(),
                        lam_ext.data_ptr<float>(), mu_hist.data_ptr<float>(),
-                       conf_indptr.data_ptr<int>(),
-                       conf_base.data_ptr<long>(),
-                       conf_cols.data_ptr<int>(), rates.data_ptr<float>(),
-                       bw_comp.data_ptr<float>(), edges.data_ptr<int>(),
-                       node_vedge.data_ptr<long>(), dlam.data_ptr<float>(),
-                       T_arr.data_ptr<float>(), E_arr.data_ptr<int>(),
-                       large, (float)cap, N, E, C, Ee, (int)iters);
+                       tables(conf_indptr, conf_base, conf_cols, rates,
+                              bw_comp, T_arr, E_arr),
+                       edges.data_ptr<int>(), node_vedge.data_ptr<long>(),
+                       dlam.data_ptr<float>(),
+                       p, (float)cap, N, E, C, Ee, (int)iters);
     return dlam;
+}
+
+// Host-only: what each queueing kernel's launcher would launch with at this
+// shape (nothing is launched).  The engine takes its per-stage fit flags
+// from here and the tests ask it which mode a shape reaches.
+py::dict queue_lds_plan(long N, long E, long Ee, long iters) {
+    using namespace pybind11::literals;
+    auto row = [](const Launch& l) {
+        return py::dict("lds_bytes"_a = l.lds_bytes, "large"_a = l.large,
+                        "threads"_a = l.threads, "fits"_a = l.fits);
+    };
+    return py::dict(
+        "critic"_a = row(critic_plan((int)E, (int)Ee, (int)iters)),
+        "actor_head_fwd"_a = row(actor_fwd_plan((int)E, (int)iters)),
+        "actor_head_bwd"_a = row(actor_bwd_plan((int)E, (int)iters)),
+        "walk_eval"_a = row(walk_plan((int)N, (int)E)));
 }

@@ -41,7 +41,9 @@ setup(
                 "multihop_offload_amd/ops/hip/optimizer.hip",
                 "multihop_offload_amd/ops/hip/chebconv_large.hip",
             ],
-            depends=["multihop_offload_amd/ops/hip/cheb_tiles.h"],
+            depends=["multihop_offload_amd/ops/hip/cheb_tiles.h",
+                     "multihop_offload_amd/ops/hip/queue_model.h",
+                     "multihop_offload_amd/ops/hip/gfx950.h"],
             extra_compile_args={
                 "cxx": ["-O3"],
                 "nvcc": ["-O3"],

@@ -78,32 +78,62 @@ def cases(name):
 
 
 @functools.lru_cache(maxsize=None)
-def engine(name, cap=0.0, dtype="float64", device="cpu", walk_cap=None):
+def engine(name, cap=0.0, dtype="float64", device="cpu", walk_cap=None,
+           fp_iters=10):
     """An EpisodeEngine over a case set (cached; the model is unused — every
     stage is fed its inputs directly)."""
     dt = getattr(torch, dtype)
     model = ChebConvStack(K=2, dtype=dt, seed=0)
     return EpisodeEngine(list(cases(name)), model, device=device, dtype=dt,
-                         delay_clamp=cap, walk_cap=walk_cap)
+                         delay_clamp=cap, walk_cap=walk_cap,
+                         fp_iters=fp_iters)
 
 
-def single_engine(name, b, cap, dtype):
+def single_engine(name, b, cap, dtype, fp_iters=10):
     dt = getattr(torch, dtype)
     return EpisodeEngine([cases(name)[b]], ChebConvStack(K=2, dtype=dt,
                                                          seed=0),
-                         device="cpu", dtype=dt, delay_clamp=cap)
+                         device="cpu", dtype=dt, delay_clamp=cap,
+                         fp_iters=fp_iters)
+
+
+def lds_plan(eng):
+    """The tests' own statement of what the four queueing kernels launch
+    with at ``eng``'s shape (anything with N, E, Ee, fp_iters), written from
+    the documented formulas and never read off the extension: LDS floats in
+    LDS-resident mode and, where the kernel has one, in global-scratch
+    ("large") mode, taken when the first is over 160 KiB; 1024 threads from
+    E >= 1500 (walk_eval also from N >= 500), else 256."""
+    E, Ee, N, it = eng.E, eng.Ee, eng.N, eng.fp_iters
+    floats = dict(
+        critic=(5 * Ee + (it + 4) * E, 2 * Ee + 3 * E),
+        actor_head_fwd=((it + 3) * E, 2 * E),
+        actor_head_bwd=((it + 6) * E, 5 * E),
+        walk_eval=(3 * E + N, None),
+    )
+    plan = {}
+    for kernel, (small, large) in floats.items():
+        is_large = large is not None and small > LDS_FLOATS
+        n = large if is_large else small
+        wide = E >= 1500 or (kernel == "walk_eval" and N >= 500)
+        plan[kernel] = dict(lds_bytes=4 * n, large=is_large,
+                            threads=1024 if wide else 256,
+                            fits=n <= LDS_FLOATS)
+    return plan
 
 
 def lds_modes(eng):
     """Which of the three queueing kernels run in global-scratch ("large")
-    mode: the launchers' own LDS formulas (ops/hip/queueing.hip) at
-    fp_iters=10, in floats."""
-    E, Ee, it = eng.E, eng.Ee, eng.fp_iters
-    return dict(
-        critic=5 * Ee + (it + 1) * E + 3 * E > LDS_FLOATS,
-        actor_head_fwd=(it + 2) * E + E > LDS_FLOATS,
-        actor_head_bwd=(it + 1) * E + 5 * E > LDS_FLOATS,
-    )
+    mode."""
+    return {k: v["large"] for k, v in lds_plan(eng).items()
+            if k != "walk_eval"}
+
+
+def lds_fits(eng):
+    """Which of the four kernels can launch at all: the large-mode limits
+    2·Ee + 3·E (critic), 2·E and 5·E (actor head), and walk_eval's
+    3·E + N, against 160 KiB."""
+    return {k: v["fits"] for k, v in lds_plan(eng).items()}
 
 
 def real_slots(eng):
@@ -166,11 +196,11 @@ def regime(eng, lam, cap):
 
 # ----------------------------------------------------- λ recipe (tests 1-2)
 @functools.lru_cache(maxsize=None)
-def lam_input(name, cap, seed=0):
+def lam_input(name, cap, seed=0, fp_iters=10):
     """λ_ext (B, Ee), fp64 holding fp32 values: λ_link = μ0·3·u,
     λ_node = bw·1.5·u with u seeded uniform, then repaired away from every
     branch boundary (marked slots ×0.8 per round).  Returns (λ, rounds)."""
-    eng = engine(name, cap)
+    eng = engine(name, cap, fp_iters=fp_iters)
     gen = torch.Generator().manual_seed(seed)
     u = torch.rand(eng.B, eng.Ee, generator=gen, dtype=torch.float64)
     mu0 = eng.link_rates / (eng.cf_degs + 1.0)
@@ -332,14 +362,14 @@ def pad_routes(route_links, H):
 
 
 @functools.lru_cache(maxsize=None)
-def front(name, walk_cap=None):
+def front(name, walk_cap=None, fp_iters=10):
     """Everything upstream of stages 3-5 from the fp64 oracle: delay matrix
     from the λ recipe (cap 0), APSP rounded to fp32, jobs, the oracle's
     decision and its integer routes.  Neither depends on the job rates, so
     the rates of jobs that put a slot inside a band (job_marks) are scaled
     by 0.8 per round until none is left."""
-    eng = engine(name, 0.0, walk_cap=walk_cap)
-    lam, _ = lam_input(name, 0.0)
+    eng = engine(name, 0.0, walk_cap=walk_cap, fp_iters=fp_iters)
+    lam, _ = lam_input(name, 0.0, fp_iters=fp_iters)
     dm, _, _ = actor_oracle(eng, lam, torch.zeros(eng.B, eng.N, eng.N,
                                                   dtype=torch.float64))
     with torch.no_grad():
@@ -356,7 +386,7 @@ def front(name, walk_cap=None):
     fr = dict(sp=sp, uds=uds, jobs=jobs, dst=dst, route_links=pad_routes(
         rl, H), nhop=nhop, overflow=overflow, H=H)
     for rounds in range(REPAIR_ROUNDS + 1):
-        bad = job_marks(name, fr)
+        bad = job_marks(name, fr, fp_iters=fp_iters)
         if not bool(bad.any()):
             break
         jobs.rates = as32(torch.where(bad, jobs.rates * 0.8, jobs.rates))
@@ -372,11 +402,16 @@ def eval_oracle(eng, fr):
         return eng.evaluate(jobs, fr["dst"], fr["route_links"], fr["nhop"])
 
 
-def critic_oracle(name, cap, dtype, fr):
+# the history stride and every carve offset of the three queueing kernels
+# depend on fp_iters; the one numeric case away from the default of 10
+FEW_ITERS = 3
+
+
+def critic_oracle(name, cap, dtype, fr, fp_iters=10):
     """Per-graph loss (B,) and grad_edge (B, Ee) of engine.critic_backward
     in ``dtype``.  The engine returns only the summed loss: per-graph losses
     come from single-case engines where B > 1."""
-    eng = engine(name, cap, dtype)
+    eng = engine(name, cap, dtype, fp_iters=fp_iters)
     jobs = jobs_to(fr["jobs"], "cpu", eng.dtype)
     rl, nhop, dst = fr["route_links"], fr["nhop"], fr["dst"]
     grad_edge, loss_sum = eng.critic_backward(jobs, dst, rl, nhop)
@@ -384,7 +419,7 @@ def critic_oracle(name, cap, dtype, fr):
         return loss_sum.reshape(1), grad_edge
     losses = []
     for b in range(eng.B):
-        e1 = single_engine(name, b, cap, dtype)
+        e1 = single_engine(name, b, cap, dtype, fp_iters)
         J1 = e1.Jmax
         assert not bool(jobs.mask[b, J1:].any())
         jb1 = JobBatch(sources=jobs.sources[b:b + 1, :J1],
@@ -441,13 +476,13 @@ def critic_units(eng, fr, cap):
     return lam, unit
 
 
-def job_marks(name, fr, caps=CRITIC_CAPS):
+def job_marks(name, fr, caps=CRITIC_CAPS, fp_iters=10):
     """(B, J) bool: jobs whose route touches a slot inside a band — for the
     critic (every cap) the three bands of band_marks on the λ the loads
     produce, plus |data·unit − 1| < BAND on a route entry; for walk_eval the
     congestion switch of the empirical evaluator on its own loads
     ((ul+dl)·rate on links, ul·rate on the destination)."""
-    eng = engine(name)
+    eng = engine(name, fp_iters=fp_iters)
     jobs, dst = fr["jobs"], fr["dst"]
     B, E = eng.B, eng.E
     seq, valid = route_entries(eng, fr)
@@ -468,14 +503,14 @@ def job_marks(name, fr, caps=CRITIC_CAPS):
     return (entry_bad & valid).any(2)
 
 
-def check_front(name, fr, caps=CRITIC_CAPS):
+def check_front(name, fr, caps=CRITIC_CAPS, fp_iters=10):
     """Conditions the fp64 oracle alone must meet for stages 3-5; returns
     the list of violated ones (empty = usable)."""
-    eng = engine(name)
+    eng = engine(name, fp_iters=fp_iters)
     jobs, nhop = fr["jobs"], fr["nhop"]
     m = jobs.mask
     bad = []
-    if bool(job_marks(name, fr, caps).any()):
+    if bool(job_marks(name, fr, caps, fp_iters).any()):
         bad.append("a job inside a band")
     if not bool((~m).any()):
         bad.append("no masked-out job")
@@ -523,11 +558,12 @@ def _actor_errs(eng, got, want):
 
 
 @functools.lru_cache(maxsize=None)
-def actor_case(name, cap):
+def actor_case(name, cap, fp_iters=10):
     """Inputs, fp64 oracle, fp32-reference errors and adopted tolerances of
     the actor-head tests."""
-    e64, e32 = engine(name, cap), engine(name, cap, "float32")
-    lam, _ = lam_input(name, cap)
+    e64 = engine(name, cap, fp_iters=fp_iters)
+    e32 = engine(name, cap, "float32", fp_iters=fp_iters)
+    lam, _ = lam_input(name, cap, fp_iters=fp_iters)
     G = cotangent(e64)
     want = actor_oracle(e64, lam, G)
     ref = _actor_errs(e64, actor_oracle(e32, lam, G), want)
@@ -544,10 +580,11 @@ def _critic_errs(eng, got, want):
 
 
 @functools.lru_cache(maxsize=None)
-def critic_case(name, cap):
-    fr = front(name)
-    want = critic_oracle(name, cap, "float64", fr)
-    ref = _critic_errs(engine(name), critic_oracle(name, cap, "float32", fr),
+def critic_case(name, cap, fp_iters=10):
+    fr = front(name, fp_iters=fp_iters)
+    want = critic_oracle(name, cap, "float64", fr, fp_iters)
+    ref = _critic_errs(engine(name),
+                       critic_oracle(name, cap, "float32", fr, fp_iters),
                        want)
     return dict(front=fr, want=want, ref=ref,
                 tol={k: tolerance(v) for k, v in ref.items()})

@@ -285,13 +285,19 @@ def test_large_mode_queueing_kernels_match_cpu():
     eg = EpisodeEngine(cases, mg, device="cuda", dtype=torch.float32)
     # the point of this test: the GPU engine must be using the kernels
     assert eg.hip_critic_ok and eg.hip_actor_ok and eg.hip_walk_ok
-    # Modes reached at this shape (E=2980; launcher LDS formulas in floats
-    # against 160 KiB = 40960): critic (5·Ee + 14·E) and actor_head_bwd
-    # (16·E) run on global scratch, actor_head_fwd (13·E, large from
-    # E >= 3151) is still LDS-resident.  All three in large mode are
-    # covered at n=430 by tests/test_gpu_stages.py (set D).
-    assert 5 * eg.Ee + 14 * eg.E > 40960 and 16 * eg.E > 40960
-    assert 13 * eg.E <= 40960
+    # Modes reached at this shape (E=2980), asked of the launchers and
+    # stated independently by stage_oracle.lds_modes (LDS floats against
+    # 160 KiB = 40960): critic (5·Ee + 14·E) and actor_head_bwd (16·E) run
+    # on global scratch, actor_head_fwd (13·E, large from E >= 3151) is
+    # still LDS-resident.  All three in large mode are covered at n=430 by
+    # tests/test_gpu_stages.py (set D).
+    from multihop_offload_amd.ops import dispatch
+    from tests import stage_oracle as so
+    plan = dispatch.require_hip().queue_lds_plan(eg.N, eg.E, eg.Ee,
+                                                 eg.fp_iters)
+    want = dict(critic=True, actor_head_bwd=True, actor_head_fwd=False)
+    assert eg.E == 2980 and so.lds_modes(eg) == want
+    assert {k: plan[k]["large"] for k in want} == want
     insts = [JobInstance.sample(g.mobile_nodes, 0.2,
                                 np.random.RandomState(3))]
     rc = ec.gnn_episode(_jobbatch_from(ec, insts), train=True)

@@ -8,6 +8,8 @@ against the fp64 oracle, per output and per set; integer and boolean
 outputs, zeros in padded slots and inf/NaN positions are exact.  Measured
 figures (fp32-reference error, adopted tolerance, kernel error on an
 MI355X) are tabulated in docs/KERNELS.md, "Stage tests"."""
+import types
+
 import numpy as np
 import pytest
 import torch
@@ -28,8 +30,8 @@ def _ext():
     return dispatch.require_hip()
 
 
-def _gpu_engine(name, cap=0.0, walk_cap=None):
-    eg = so.engine(name, cap, "float32", "cuda", walk_cap)
+def _gpu_engine(name, cap=0.0, walk_cap=None, fp_iters=10):
+    eg = so.engine(name, cap, "float32", "cuda", walk_cap, fp_iters)
     assert eg.use_hip
     return eg
 
@@ -62,24 +64,89 @@ def _actor_kernels(eg, lam, G):
     return dm, hist, dlam
 
 
+def _plan(eng):
+    """The launchers' own plan at an engine's (or any) shape."""
+    return _ext().queue_lds_plan(eng.N, eng.E, eng.Ee, eng.fp_iters)
+
+
 @needs_gpu
 def test_set_d_runs_all_three_queueing_kernels_in_large_mode():
-    """The launchers' LDS formulas (floats, 160 KiB = 40960): critic
-    5·Ee + 14·E, actor_head_fwd 13·E, actor_head_bwd 16·E.  Set D
-    (E=3220, Ee=3649) is over all three and at E >= 1500 launches 1024
-    threads, while walk_eval's 3·E + N still fits LDS; sets A-C are under
-    all three."""
+    """Asked of the launchers (ext.queue_lds_plan) and stated independently
+    (so.lds_plan: critic 5·Ee + 14·E, actor_head_fwd 13·E, actor_head_bwd
+    16·E floats against 160 KiB = 40960): set D (E=3220, Ee=3649) is over
+    all three and at E >= 1500 launches 1024 threads, while walk_eval's
+    3·E + N still fits LDS; sets A-C are under all three."""
     eg = _gpu_engine("D")
-    E, Ee, N = eg.E, eg.Ee, eg.N
-    assert 5 * Ee + 14 * E > 40960          # critic
-    assert 13 * E > 40960                   # actor_head_fwd
-    assert 16 * E > 40960                   # actor_head_bwd
-    assert E >= 1500
-    assert (3 * E + N) * 4 <= 160 * 1024 and eg.hip_walk_ok
-    assert eg.hip_critic_ok and eg.hip_actor_ok
+    plan, want = _plan(eg), so.lds_modes(eg)
+    assert all(want.values())
+    assert {k: plan[k]["large"] for k in want} == want
+    assert eg.E >= 1500
+    assert all(p["threads"] == 1024 for p in plan.values())
+    walk = plan["walk_eval"]
+    assert walk["fits"] and not walk["large"] and so.lds_fits(eg)["walk_eval"]
+    assert eg.hip_walk_ok and eg.hip_critic_ok and eg.hip_actor_ok
     for name in "ABC":
         e = _gpu_engine(name)
-        assert 5 * e.Ee + 14 * e.E <= 40960 and 16 * e.E <= 40960
+        assert not any(so.lds_modes(e).values())
+        assert not any(p["large"] for p in _plan(e).values())
+
+
+def _shape(N, E, Ee, fp_iters):
+    return types.SimpleNamespace(N=N, E=E, Ee=Ee, fp_iters=fp_iters)
+
+
+def _last_small(kernel, fp_iters):
+    """Largest E (Ee = E + 8, N = 430) at which so.lds_plan keeps ``kernel``
+    LDS-resident."""
+    E = 1
+    while not so.lds_plan(_shape(430, E + 1, E + 9, fp_iters))[kernel]["large"]:
+        E += 1
+    return E
+
+
+def test_queue_lds_plan_matches_the_stated_formulas():
+    """ext.queue_lds_plan (host only, nothing is launched) against
+    so.lds_plan, which states the formulas on its own: lds_bytes, large,
+    threads and fits of all four kernels on sets A-D and on both sides of
+    every switch point, at fp_iters 10 and 3.  At 10 the switches are
+    E = 3150/3151 (actor_head_fwd, 13·E), 2560/2561 (actor_head_bwd, 16·E)
+    and 2153/2154 with Ee = E + 8 (critic, 5·Ee + 14·E); the large-mode
+    limits of the actor head are 5·E at E = 8192/8193 and 2·E at
+    20480/20481, walk_eval's 3·E + N at N = 430 is E = 13510/13511, and the
+    thread count changes at E = 1499/1500 and, for walk_eval, N = 499/500."""
+    try:
+        ext = _ext()
+    except RuntimeError:
+        pytest.skip("HIP extension not built")
+    assert _last_small("actor_head_fwd", 10) == 3150
+    assert _last_small("actor_head_bwd", 10) == 2560
+    assert _last_small("critic", 10) == 2153
+    shapes = []
+    for it in (10, so.FEW_ITERS):
+        for name in so.SETS:
+            e = so.engine(name)
+            shapes.append(_shape(e.N, e.E, e.Ee, it))
+        for kernel in ("actor_head_fwd", "actor_head_bwd", "critic"):
+            E = _last_small(kernel, it)
+            shapes += [_shape(430, E, E + 8, it), _shape(430, E + 1, E + 9, it)]
+        for E in (8192, 8193, 20480, 20481, 13510, 13511, 1499, 1500):
+            shapes.append(_shape(430, E, E + 8, it))
+        for N in (499, 500):
+            shapes.append(_shape(N, 1499, 1507, it))
+    seen = {k: set() for k in ("large", "fits", "threads")}
+    for sh in shapes:
+        got = ext.queue_lds_plan(sh.N, sh.E, sh.Ee, sh.fp_iters)
+        want = so.lds_plan(sh)
+        assert got == want, (vars(sh), got, want)
+        for kernel, p in want.items():
+            for k in seen:
+                seen[k].add((kernel, p[k]))
+    # the cases reach both values of every field for every kernel that has two
+    kernels = ("critic", "actor_head_fwd", "actor_head_bwd", "walk_eval")
+    for kernel in kernels:
+        assert {(kernel, 256), (kernel, 1024)} <= seen["threads"]
+        assert {(kernel, True), (kernel, False)} <= seen["fits"]
+        assert ((kernel, True) in seen["large"]) == (kernel != "walk_eval")
 
 
 @needs_gpu
@@ -118,6 +185,22 @@ def test_actor_head_bwd_vs_fp64(name, cap):
     _check("actor_head_bwd", name, f"cap {cap}", {"dlam": errs["dlam"]}, c)
 
 
+def _critic_kernel(eg, fr):
+    jobs = so.jobs_to(fr["jobs"], "cuda", torch.float32)
+    dst = fr["dst"].cuda()
+    ge, loss = _ext().critic(
+        fr["route_links"].to(torch.int32).cuda().contiguous(),
+        fr["nhop"].to(torch.int32).cuda().contiguous(),
+        eg.node_vedge.gather(1, dst).contiguous(), jobs.mask,
+        jobs.rates.contiguous(), jobs.ul.contiguous(), jobs.dl.contiguous(),
+        eg.k_conf_indptr, eg.k_conf_base, eg.k_conf_cols,
+        eg.link_rates.contiguous(), eg.bw_comp.contiguous(), eg.k_E_arr,
+        eg.T_arr.contiguous(), eg.Ee, eg.fp_iters, eg.delay_clamp)
+    torch.cuda.synchronize()
+    assert loss.shape == (eg.B,) and ge.shape == (eg.B, eg.Ee)
+    return loss, ge
+
+
 @needs_gpu
 @pytest.mark.parametrize("name,cap", CRITIC)
 def test_critic_vs_fp64(name, cap):
@@ -131,22 +214,37 @@ def test_critic_vs_fp64(name, cap):
     little from run to run with the order of the atomics): loss up to
     1.2e-7, grad_edge up to 2.1e-7 (docs/KERNELS.md)."""
     c = so.critic_case(name, cap)
-    fr = c["front"]
-    eg = _gpu_engine(name, cap)
-    jobs = so.jobs_to(fr["jobs"], "cuda", torch.float32)
-    dst = fr["dst"].cuda()
-    ge, loss = _ext().critic(
-        fr["route_links"].to(torch.int32).cuda().contiguous(),
-        fr["nhop"].to(torch.int32).cuda().contiguous(),
-        eg.node_vedge.gather(1, dst).contiguous(), jobs.mask,
-        jobs.rates.contiguous(), jobs.ul.contiguous(), jobs.dl.contiguous(),
-        eg.k_conf_indptr, eg.k_conf_base, eg.k_conf_cols,
-        eg.link_rates.contiguous(), eg.bw_comp.contiguous(), eg.k_E_arr,
-        eg.T_arr.contiguous(), eg.Ee, eg.fp_iters, eg.delay_clamp)
-    torch.cuda.synchronize()
-    assert loss.shape == (eg.B,) and ge.shape == (eg.B, eg.Ee)
+    loss, ge = _critic_kernel(_gpu_engine(name, cap), c["front"])
     errs = so._critic_errs(so.engine(name), (loss, ge), c["want"])
     _check("critic", name, f"cap {cap}", errs, c)
+
+
+@needs_gpu
+@pytest.mark.parametrize("cap", so.CRITIC_CAPS)
+def test_queueing_kernels_at_three_iterations_vs_fp64(cap):
+    """actor_head_fwd, actor_head_bwd and critic on set A at fp_iters = 3
+    (every other test runs 10): the stride of the mu history and every LDS
+    carve offset depend on it.  Same recipes, metrics and fp64 oracle as the
+    tests above, with the inputs repaired and the fp32-reference errors
+    measured on 3-iteration engines (conditioning proven in
+    tests/test_stage_inputs.py).  CPU fp32-reference errors: dm
+    3.1e-7..1.5e-6, mu_hist 1.7e-7, dlam 1.9e-7..3.2e-6, loss
+    8.8e-8..1.2e-7, grad_edge 1.5e-7 -> tolerances 9.5e-7..2.6e-5.  Kernel
+    errors on an MI355X: dm, mu_hist and dlam at clamp 0 equal to the
+    reference errors, dlam 1.4e-7 at clamp 0.5, loss 1.2e-7, grad_edge
+    6.7e-8 (per output and clamp in docs/KERNELS.md)."""
+    it = so.FEW_ITERS
+    a = so.actor_case("A", cap, it)
+    eg = _gpu_engine("A", cap, fp_iters=it)
+    assert eg.fp_iters == it
+    got = _actor_kernels(eg, a["lam"], a["G"])
+    assert got[1].shape == (eg.B, it + 1, eg.E)
+    errs = so._actor_errs(so.engine("A", cap, fp_iters=it), got, a["want"])
+    _check("actor_head", "A", f"cap {cap} fp_iters {it}", errs, a)
+    c = so.critic_case("A", cap, it)
+    loss, ge = _critic_kernel(eg, c["front"])
+    errs = so._critic_errs(so.engine("A"), (loss, ge), c["want"])
+    _check("critic", "A", f"cap {cap} fp_iters {it}", errs, c)
 
 
 def _decide(eg, jobs, sp, uds):

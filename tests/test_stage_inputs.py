@@ -29,7 +29,7 @@ def test_shapes_reach_the_documented_paths():
         assert all(large.values()) == (name == "D")
         assert any(large.values()) == (name == "D")
         assert (eng.E >= 1500) == (name == "D")
-        assert eng.hip_walk_ok and eng.hip_critic_ok and eng.hip_actor_ok
+        assert all(so.lds_fits(eng).values())
     assert so.engine("B").E_list == [160, 158, 182]          # ragged E
     assert so.engine("C").E_list == [36, 46]
     assert so.engine("C").k_N_arr.tolist() == [20, 25]       # inert pad nodes
@@ -144,3 +144,30 @@ def test_walk_eval_reference_errors(name, walk_cap):
         print(f"walk_eval set {name} walk_cap {walk_cap} {k}: fp32-reference "
               f"error {c['ref'][k]:.3e} -> tolerance {c['tol'][k]:.3e}")
         assert c["tol"][k] <= so.TOL_CEILING
+
+
+@pytest.mark.parametrize("cap", so.CRITIC_CAPS)
+def test_three_iteration_inputs_are_conditioned(cap):
+    """Set A at fp_iters = 3 (the one numeric case away from 10): λ and the
+    job rates are repaired on 3-iteration engines, reach both delay
+    branches, and the tolerances stay under the ceiling."""
+    it = so.FEW_ITERS
+    eng = so.engine("A", cap, fp_iters=it)
+    assert eng.fp_iters == it
+    lam, rounds = so.lam_input("A", cap, fp_iters=it)
+    assert rounds <= so.REPAIR_ROUNDS
+    assert not bool(so.band_marks(eng, lam, cap).any())
+    assert so.mu_history(eng, lam[:, :eng.E]).shape[1] == it + 1
+    cong, _ = so.regime(eng, lam, cap)
+    lk = eng.link_mask
+    assert bool((cong[:, :eng.E] & lk).any())
+    assert bool((~cong[:, :eng.E] & lk).any())
+    fr = so.front("A", fp_iters=it)
+    assert fr["rounds"] <= so.REPAIR_ROUNDS
+    assert so.check_front("A", fr, so.CRITIC_CAPS, it) == []
+    for what, c in (("actor", so.actor_case("A", cap, it)),
+                    ("critic", so.critic_case("A", cap, it))):
+        for k in c["ref"]:
+            print(f"{what} set A cap {cap} fp_iters {it} {k}: fp32-reference "
+                  f"error {c['ref'][k]:.3e} -> tolerance {c['tol'][k]:.3e}")
+            assert c["tol"][k] <= so.TOL_CEILING
