@@ -81,7 +81,8 @@ class EpisodeEngine:
     def __init__(self, cases: Sequence[CaseGraph], model: ChebConvStack,
                  device: str = "cpu", dtype: torch.dtype = torch.float32,
                  fp_iters: int = 10, walk_cap: Optional[int] = None,
-                 delay_clamp: float = 0.0, lam_margin: float = 0.0):
+                 delay_clamp: float = 0.0, lam_margin: float = 0.0,
+                 native_glue: bool = True):
         assert len(cases) > 0
         N = cases[0].num_nodes
         T = cases[0].T
@@ -352,6 +353,11 @@ class EpisodeEngine:
             self.hip_critic_ok = plan["critic"]["fits"]
             self.hip_actor_ok = (plan["actor_head_fwd"]["fits"]
                                  and plan["actor_head_bwd"]["fits"])
+        # the per-step glue between the episode kernels (features, parameter
+        # pack / gradient reduce, APSP prep, actor cotangent, summary, job
+        # sampling after the draws) as HIP kernels; False keeps the torch
+        # glue around the same episode kernels (the oracle of the glue tests)
+        self.native_glue = bool(native_glue) and self.use_hip
 
     def set_rng_seed(self, seed: int):
         """Seed the in-kernel stateless sampler (per-DP-rank seeds keep the
@@ -367,23 +373,41 @@ class EpisodeEngine:
         U(0.1,0.5)·scale, ul=100, dl=1."""
         B, N, J = self.B, self.N, self.Jmax
         dev = self.device
-        scores = torch.rand(B, N, device=dev, generator=gen)
-        scores = torch.where(self.mobile_mask, scores,
-                             torch.full_like(scores, 2.0))
+        scores_raw = torch.rand(B, N, device=dev, generator=gen)
+        r_nj = torch.rand(B, device=dev, generator=gen)
+        r_rates = torch.rand(B, J, device=dev, generator=gen)
+        return self._jobs_from_draws(scores_raw, r_nj, r_rates,
+                                     arrival_scale)
+
+    def _jobs_from_draws(self, scores_raw: torch.Tensor, r_nj: torch.Tensor,
+                         r_rates: torch.Tensor,
+                         arrival_scale: float) -> JobBatch:
+        """Everything of ``sample_jobs`` after the three uniform draws: one
+        HIP launch on the native path, the torch composition otherwise (the
+        two agree exactly; equal scores among mobiles — a 2^-24 event per
+        pair — are ordered by node id in the kernel)."""
+        J = self.Jmax
+        dev = self.device
+        if self.native_glue:
+            sources, mask, rates, ul, dl = ops.require_hip().jobs_from_draws(
+                scores_raw, r_nj, r_rates, self.mobile_mask,
+                float(arrival_scale))
+            return JobBatch(sources=sources, mask=mask, rates=rates, ul=ul,
+                            dl=dl)
+        scores = torch.where(self.mobile_mask, scores_raw,
+                             torch.full_like(scores_raw, 2.0))
         order = torch.argsort(scores, dim=1)                 # mobiles first
         sources = order[:, :J]                               # (B,J)
         M = self.mobile_mask.sum(1)                          # (B,)
         lo = (0.3 * M).to(torch.int64)
         span = (M - lo).clamp(min=1)
-        nj = lo + (torch.rand(B, device=dev, generator=gen)
-                   * span.to(self.dtype)).to(torch.int64)
+        nj = lo + (r_nj * span.to(self.dtype)).to(torch.int64)
         nj = nj.clamp(min=1)
         mask = torch.arange(J, device=dev)[None, :] < nj[:, None]
         # clamp padded sources to a valid mobile (first sampled) for safety
         sources = torch.where(mask, sources, sources[:, :1])
-        rates = (torch.rand(B, J, device=dev, generator=gen) * 0.4 + 0.1) \
-            * arrival_scale
-        z = torch.zeros(B, J, device=dev, dtype=self.dtype)
+        rates = (r_rates * 0.4 + 0.1) * arrival_scale
+        z = torch.zeros(self.B, J, device=dev, dtype=self.dtype)
         return JobBatch(
             sources=sources,
             mask=mask,
@@ -425,11 +449,15 @@ class EpisodeEngine:
         )
 
     # ------------------------------------------------------- actor forward
-    def actor_forward(self, jobs: JobBatch):
-        """features → ChebConv → λ → fixed point → delays → (B,N,N) delay
-        matrix (autograd graph kept).  Reference gnn_offloading_agent.py:
-        211-276, batched."""
-        B, E, Ee, N = self.B, self.E, self.Ee, self.N
+    def _features(self, jobs: JobBatch) -> torch.Tensor:
+        """x (B,Ē,4) = [self-loop, rate, job load, as-server]: the job load
+        Σ rate·ul lands on the virtual edge of each job's source."""
+        if self.native_glue:
+            return ops.require_hip().cheb_features(
+                jobs.sources, jobs.rates.contiguous(), jobs.ul.contiguous(),
+                jobs.mask, self.node_vedge, self.comp_mask, self.f_self_loop,
+                self.f_rate, self.f_as_server)
+        B, Ee, N = self.B, self.Ee, self.N
         arr = torch.zeros(B, N, dtype=self.dtype, device=self.device)
         arr = arr.scatter_add(1, jobs.sources, jobs.rates * jobs.ul)
         f_job = torch.zeros(B, Ee, dtype=self.dtype, device=self.device)
@@ -437,34 +465,81 @@ class EpisodeEngine:
                            torch.zeros_like(self.node_vedge))
         f_job = f_job.scatter_add(
             1, vidx, torch.where(self.comp_mask, arr, torch.zeros_like(arr)))
+        return torch.stack([self.f_self_loop, self.f_rate, f_job,
+                            self.f_as_server], dim=-1)
 
-        x = torch.stack([self.f_self_loop, self.f_rate, f_job,
-                         self.f_as_server], dim=-1)               # (B,Ē,4)
+    def _actor_head_tables(self):
+        """The batch tables the actor-head kernels take after λ (forward)
+        or after (cotangent, λ, mu_hist) (backward)."""
+        return (self.k_conf_indptr, self.k_conf_base, self.k_conf_cols,
+                self.link_rates.contiguous(), self.bw_comp.contiguous(),
+                self.k_edges, self.node_vedge, self.T_arr.contiguous(),
+                self.k_E_arr)
 
+    def _lam_hip(self, jobs: JobBatch) -> torch.Tensor:
+        """features → ChebConv → λ (B,Ē) on the HIP path (autograd graph
+        kept)."""
+        B, Ee = self.B, self.Ee
+        x = self._features(jobs)                                  # (B,Ē,4)
+        from .ops.functions import ChebStackFn, cheb_compat
+        if cheb_compat(self.model):
+            params = []
+            for layer in self.model.layers:
+                params += [layer.weight, layer.bias]
+            lam = ChebStackFn.apply(x.contiguous(), self, *params)
+        else:
+            # no silent eager fallback on GPU: unsupported model
+            # shapes refuse loudly unless explicitly overridden
+            import os as _os
+            if _os.environ.get("MHO_ALLOW_TORCH_GPU") != "1":
+                raise RuntimeError(
+                    "model shape unsupported by the fused ChebConv "
+                    "kernels (feature width > 32 or dropout > 0); "
+                    "refusing eager torch on GPU — set "
+                    "MHO_ALLOW_TORCH_GPU=1 to override")
+            return self.model(x.reshape(B * Ee, 4),
+                              self.support).reshape(B, Ee)
+        if self.lam_margin:
+            lam = lam * (1.0 + self.lam_margin)
+        return lam
+
+    def _actor_forward_native(self, jobs: JobBatch):
+        """``actor_forward`` of the native-glue episode: the head runs
+        outside autograd, because its backward takes the cotangent as
+        (grad_edge, unit_mtx, written) and never as a dense (B,N,N) tensor.
+        Returns (dm without a graph, saved) with ``saved`` what
+        ``_actor_backward_native`` needs."""
+        lam = self._lam_hip(jobs)
+        lam_c = lam.detach().contiguous()
+        dm, mu_hist = ops.require_hip().actor_head_fwd(
+            lam_c, *self._actor_head_tables(), self.N, self.fp_iters,
+            self.delay_clamp)
+        return dm, (lam, lam_c, mu_hist)
+
+    def _actor_backward_native(self, saved, grad_edge, dm, unit_mtx,
+                               written):
+        """Actor backward of the native-glue episode: the head's VJP with
+        the cotangent assembled in the kernel (``grad_dist_matrix`` fused
+        into ``actor_head_bwd``), then autograd through the ChebConv stack.
+        Returns loss_mse."""
+        lam, lam_c, mu_hist = saved
+        dlam, loss_mse = ops.require_hip().actor_head_bwd_fused(
+            grad_edge.contiguous(), dm, unit_mtx, written, lam_c, mu_hist,
+            *self._actor_head_tables(), self.fp_iters, self.delay_clamp)
+        lam.backward(dlam)
+        return loss_mse
+
+    def actor_forward(self, jobs: JobBatch):
+        """features → ChebConv → λ → fixed point → delays → (B,N,N) delay
+        matrix (autograd graph kept).  Reference gnn_offloading_agent.py:
+        211-276, batched."""
+        B, E, Ee, N = self.B, self.E, self.Ee, self.N
         if self.use_hip and self.hip_actor_ok:
-            from .ops.functions import ActorHeadFn, ChebStackFn, cheb_compat
-            if cheb_compat(self.model):
-                params = []
-                for layer in self.model.layers:
-                    params += [layer.weight, layer.bias]
-                lam = ChebStackFn.apply(x.contiguous(), self, *params)
-                if self.lam_margin:
-                    lam = lam * (1.0 + self.lam_margin)
-            else:
-                # no silent eager fallback on GPU: unsupported model
-                # shapes refuse loudly unless explicitly overridden
-                import os as _os
-                if _os.environ.get("MHO_ALLOW_TORCH_GPU") != "1":
-                    raise RuntimeError(
-                        "model shape unsupported by the fused ChebConv "
-                        "kernels (feature width > 32 or dropout > 0); "
-                        "refusing eager torch on GPU — set "
-                        "MHO_ALLOW_TORCH_GPU=1 to override")
-                lam = self.model(x.reshape(B * Ee, 4),
-                                 self.support).reshape(B, Ee)
-            dm = ActorHeadFn.apply(lam, self)
+            from .ops.functions import ActorHeadFn
+            dm = ActorHeadFn.apply(self._lam_hip(jobs), self)
             return dm, None, None
 
+        x = self._features(jobs)                                  # (B,Ē,4)
         lam = self.model(x.reshape(B * Ee, 4), self.support).reshape(B, Ee)
         if self.lam_margin:
             lam = lam * (1.0 + self.lam_margin)
@@ -507,6 +582,11 @@ class EpisodeEngine:
         tape too, gnn_offloading_agent.py:304-306)."""
         B, N = self.B, self.N
         with torch.no_grad():
+            if self.native_glue:
+                # mask and diagonal applied in the kernel's LDS load
+                return ops.require_hip().floyd_warshall_dm(
+                    dm.detach(), self.adj,
+                    self.k_N_arr if self._padded else None)
             w = torch.where(self.adj, dm.detach(),
                             torch.full_like(dm, float("inf")))
             w = torch.where(self._eye, torch.zeros_like(w), w)
@@ -883,8 +963,12 @@ class EpisodeEngine:
         replay-memory unit, gnn_offloading_agent.py:141-169), extracted from
         the per-graph dW/db partials of the fused ChebConv backward."""
         ctx = torch.enable_grad() if train else torch.no_grad()
+        native_bwd = self.native_glue and self.hip_actor_ok
         with ctx:
-            dm, link_delay, node_delay = self.actor_forward(jobs)
+            if native_bwd:
+                dm, actor_saved = self._actor_forward_native(jobs)
+            else:
+                dm, link_delay, node_delay = self.actor_forward(jobs)
         sp = self.apsp(dm)
         uds = torch.diagonal(dm.detach(), dim1=1, dim2=2)     # (B,N)
         dst, est = self.offload_decide(jobs, sp, uds, explore, gen, prob)
@@ -910,9 +994,13 @@ class EpisodeEngine:
         if train:
             grad_edge, loss_fn = self.critic_backward(jobs, dst, route_links,
                                                       nhop)
-            grad_dist, loss_mse = self.grad_dist_matrix(
-                grad_edge, dm, unit_mtx, written)
             self.per_sample_request = per_sample
+            if native_bwd:
+                loss_mse = self._actor_backward_native(
+                    actor_saved, grad_edge, dm, unit_mtx, written)
+            else:
+                grad_dist, loss_mse = self.grad_dist_matrix(
+                    grad_edge, dm, unit_mtx, written)
             if per_sample and not self.use_hip:
                 # CPU/torch fallback: instances are independent blocks, so
                 # a masked cotangent per graph yields its gradient set
@@ -930,16 +1018,28 @@ class EpisodeEngine:
                 self.last_per_sample_grads = out
                 dm.backward(grad_dist)
             else:
-                dm.backward(grad_dist)
+                if not native_bwd:
+                    dm.backward(grad_dist)
                 if per_sample:
                     self.last_per_sample_grads = \
                         self._collect_per_sample_grads()
             self.per_sample_request = False
 
-        nj = jobs.mask.sum(1)
-        de = torch.where(jobs.mask, delay_emp, torch.zeros_like(delay_emp))
-        tau = de.sum(1) / nj.to(self.dtype)
-        congest = ((delay_emp > self.T_arr[:, None]) & jobs.mask).sum(1)
+        return self._result(jobs, delay_emp, loss_fn, loss_mse)
+
+    def _result(self, jobs: JobBatch, delay_emp: torch.Tensor,
+                loss_fn=None, loss_mse=None) -> EpisodeResult:
+        """Per-graph summary of an episode: mean delay over the real jobs,
+        congested-job and job counts (one HIP launch on the native path)."""
+        if self.native_glue:
+            tau, congest, nj = ops.require_hip().episode_summary(
+                delay_emp.contiguous(), jobs.mask, self.T_arr)
+        else:
+            nj = jobs.mask.sum(1)
+            de = torch.where(jobs.mask, delay_emp,
+                             torch.zeros_like(delay_emp))
+            tau = de.sum(1) / nj.to(self.dtype)
+            congest = ((delay_emp > self.T_arr[:, None]) & jobs.mask).sum(1)
         return EpisodeResult(tau=tau, congest=congest, num_jobs=nj,
                              delay_emp=delay_emp, loss_fn=loss_fn,
                              loss_mse=loss_mse)
@@ -981,12 +1081,7 @@ class EpisodeEngine:
                               dproc, torch.full_like(dproc, float("inf")))
             dst, est = self.offload_decide(jobs, sp, uds)
             _, _, delay_emp, _, _ = self._episode_eval(jobs, dst, sp)
-            nj = jobs.mask.sum(1)
-            de = torch.where(jobs.mask, delay_emp, torch.zeros_like(delay_emp))
-            return EpisodeResult(
-                tau=de.sum(1) / nj.to(self.dtype),
-                congest=((delay_emp > self.T_arr[:, None]) & jobs.mask).sum(1),
-                num_jobs=nj, delay_emp=delay_emp)
+            return self._result(jobs, delay_emp)
 
     def local_episode(self, jobs: JobBatch) -> EpisodeResult:
         """Local computing (offloading_v3.py:363-386), batched."""
@@ -1004,9 +1099,4 @@ class EpisodeEngine:
                 nhop = torch.zeros(B, J, dtype=torch.int64,
                                    device=self.device)
                 delay_emp, *_ = self.evaluate(jobs, dst, route_links, nhop)
-            nj = jobs.mask.sum(1)
-            de = torch.where(jobs.mask, delay_emp, torch.zeros_like(delay_emp))
-            return EpisodeResult(
-                tau=de.sum(1) / nj.to(self.dtype),
-                congest=((delay_emp > self.T_arr[:, None]) & jobs.mask).sum(1),
-                num_jobs=nj, delay_emp=delay_emp)
+            return self._result(jobs, delay_emp)

@@ -51,7 +51,11 @@ class ChebStackFn(torch.autograd.Function):
     def forward(ctx, x: torch.Tensor, eng, *params):
         ext = dispatch.require_hip()
         K = params[0].shape[0]
-        Wp, bp = pack_cheb_params(params)
+        ctx.native = bool(getattr(eng, "native_glue", False))
+        if ctx.native:
+            Wp, bp = ext.cheb_pack_params(list(params))
+        else:
+            Wp, bp = pack_cheb_params(params)
         ctx.K = K
         ctx.large = not cheb_lds_fits(eng.Ee, K)
         if K > 2:
@@ -77,6 +81,7 @@ class ChebStackFn(torch.autograd.Function):
         ctx.save_for_backward(acts, Wp)
         ctx.eng = eng
         ctx.shapes = [tuple(p.shape) for p in params]
+        ctx.params = params
         return lam
 
     @staticmethod
@@ -98,6 +103,8 @@ class ChebStackFn(torch.autograd.Function):
                                   eng.k_ext_cols, eng.k_ext_max_nnz)
         if getattr(eng, "per_sample_request", False):
             eng._per_sample_raw = (dW, db)   # per-graph partials, pre-sum
+        if ctx.native:
+            return (None, None, *_reduce_grads_native(ext, ctx, dW, db))
         dW = dW.sum(dim=0)            # (L,K,32,32) summed over graphs
         db = db.sum(dim=0)            # (L,32)
         grads = []
@@ -106,6 +113,32 @@ class ChebStackFn(torch.autograd.Function):
             grads.append(dW[l, :kw, :fi, :fo].contiguous())
             grads.append(db[l, :ctx.shapes[2 * l + 1][0]].contiguous())
         return (None, None, *grads)
+
+
+def _reduce_grads_native(ext, ctx, dW, db):
+    """Sum the per-graph partials over B and unpad them in one launch.  When
+    a FusedAdam owns every parameter's ``.grad`` (they are the recorded views
+    of its flat buffer) the sums are added straight into that buffer and
+    autograd gets no gradients to accumulate; otherwise the gradients are
+    views of one fresh flat buffer."""
+    shapes = [list(s) for s in ctx.shapes]
+    numels = [p.numel() for p in ctx.params]
+    owner = getattr(ctx.eng.model, "_fused_grad_owner", None)
+    if owner is not None:
+        flat_g, offsets = owner
+        if len(offsets) == len(ctx.params) and all(
+                p.grad is not None and p.grad.is_contiguous()
+                and p.grad.shape == p.shape
+                and p.grad.data_ptr() == flat_g.data_ptr() + 4 * off
+                for p, off in zip(ctx.params, offsets)):
+            ext.cheb_reduce_grads(dW, db, shapes, flat_g, list(offsets),
+                                  True)
+            return [None] * len(ctx.params)
+    offsets = [sum(numels[:i]) for i in range(len(numels))]
+    flat = dW.new_empty(sum(numels))
+    ext.cheb_reduce_grads(dW, db, shapes, flat, offsets, False)
+    return [flat[o:o + k].view(s)
+            for o, k, s in zip(offsets, numels, ctx.shapes)]
 
 
 class ActorHeadFn(torch.autograd.Function):
@@ -120,11 +153,8 @@ class ActorHeadFn(torch.autograd.Function):
     def forward(ctx, lam_ext: torch.Tensor, eng):
         ext = dispatch.require_hip()
         dm, mu_hist = ext.actor_head_fwd(
-            lam_ext.contiguous(), eng.k_conf_indptr, eng.k_conf_base,
-            eng.k_conf_cols, eng.link_rates.contiguous(),
-            eng.bw_comp.contiguous(), eng.k_edges, eng.node_vedge,
-            eng.T_arr.contiguous(), eng.k_E_arr, eng.N, eng.fp_iters,
-            eng.delay_clamp)
+            lam_ext.contiguous(), *eng._actor_head_tables(), eng.N,
+            eng.fp_iters, eng.delay_clamp)
         ctx.save_for_backward(lam_ext, mu_hist)
         ctx.eng = eng
         return dm
@@ -136,10 +166,7 @@ class ActorHeadFn(torch.autograd.Function):
         ext = dispatch.require_hip()
         dlam = ext.actor_head_bwd(
             grad_dist.contiguous(), lam_ext.contiguous(), mu_hist,
-            eng.k_conf_indptr, eng.k_conf_base, eng.k_conf_cols,
-            eng.link_rates.contiguous(), eng.bw_comp.contiguous(),
-            eng.k_edges, eng.node_vedge, eng.T_arr.contiguous(),
-            eng.k_E_arr, eng.fp_iters, eng.delay_clamp)
+            *eng._actor_head_tables(), eng.fp_iters, eng.delay_clamp)
         return dlam, None
 
 
@@ -177,6 +204,9 @@ class FusedAdam:
                     segs.append([off, k, 0, 0, 0])
                 off += k
         self.seg = _t.tensor(segs, dtype=_t.int32, device=dev)
+        # lets the ChebConv backward add its gradients straight into flat_g
+        # (functions._reduce_grads_native) while the .grad views stay these
+        model._fused_grad_owner = (self.flat_g, [s[0] for s in segs])
         self.lr, self.betas, self.eps = lr, betas, eps
         self.constraints = constraints
 

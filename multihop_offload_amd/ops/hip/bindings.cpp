@@ -37,7 +37,35 @@ torch::Tensor actor_head_bwd_hip(
     torch::Tensor conf_cols, torch::Tensor rates, torch::Tensor bw_comp,
     torch::Tensor edges, torch::Tensor node_vedge, torch::Tensor T_arr,
     torch::Tensor E_arr, long iters, double cap);
+std::vector<torch::Tensor> actor_head_bwd_fused_hip(
+    torch::Tensor grad_edge, torch::Tensor dm, torch::Tensor unit_mtx,
+    torch::Tensor written, torch::Tensor lam_ext, torch::Tensor mu_hist,
+    torch::Tensor conf_indptr, torch::Tensor conf_base,
+    torch::Tensor conf_cols, torch::Tensor rates, torch::Tensor bw_comp,
+    torch::Tensor edges, torch::Tensor node_vedge, torch::Tensor T_arr,
+    torch::Tensor E_arr, long iters, double cap);
+torch::Tensor floyd_warshall_dm_hip(torch::Tensor dm, torch::Tensor adj,
+                                    c10::optional<torch::Tensor> n_arr);
 py::dict queue_lds_plan(long N, long E, long Ee, long iters);
+
+// step_glue.hip
+std::vector<torch::Tensor> cheb_pack_params_hip(
+    std::vector<torch::Tensor> params);
+void cheb_reduce_grads_hip(torch::Tensor dW, torch::Tensor db,
+                           std::vector<std::vector<int64_t>> shapes,
+                           torch::Tensor flat_out,
+                           std::vector<int64_t> offsets, bool accumulate);
+torch::Tensor cheb_features_hip(
+    torch::Tensor sources, torch::Tensor rates, torch::Tensor ul,
+    torch::Tensor mask, torch::Tensor node_vedge, torch::Tensor comp_mask,
+    torch::Tensor f_self_loop, torch::Tensor f_rate,
+    torch::Tensor f_as_server);
+std::vector<torch::Tensor> episode_summary_hip(torch::Tensor delay_emp,
+                                               torch::Tensor mask,
+                                               torch::Tensor T_arr);
+std::vector<torch::Tensor> jobs_from_draws_hip(
+    torch::Tensor scores_raw, torch::Tensor r_nj, torch::Tensor r_rates,
+    torch::Tensor mobile_mask, double arrival_scale);
 
 std::vector<torch::Tensor> cheb_fwd_hip(
     torch::Tensor x, torch::Tensor W, torch::Tensor bias,
@@ -82,6 +110,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("critic", &critic_hip);
     m.def("actor_head_fwd", &actor_head_fwd_hip);
     m.def("actor_head_bwd", &actor_head_bwd_hip);
+    m.def("actor_head_bwd_fused", &actor_head_bwd_fused_hip);
+    m.def("floyd_warshall_dm", &floyd_warshall_dm_hip);
+    m.def("cheb_pack_params", &cheb_pack_params_hip);
+    m.def("cheb_reduce_grads", &cheb_reduce_grads_hip);
+    m.def("cheb_features", &cheb_features_hip);
+    m.def("episode_summary", &episode_summary_hip);
+    m.def("jobs_from_draws", &jobs_from_draws_hip);
     m.def("queue_lds_plan", &queue_lds_plan);
     m.def("cheb_fwd", &cheb_fwd_hip);
     m.def("cheb_bwd", &cheb_bwd_hip);

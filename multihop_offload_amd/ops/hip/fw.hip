@@ -27,12 +27,21 @@ namespace {
 // (staged at compact stride n in LDS) — pad nodes are isolated, so their
 // +inf rows in global memory are already final.  O(n³) instead of O(N³)
 // per graph: a 20-node case padded to 120 does 216× less work.
-template <typename T>
-__global__ void fw_lds_kernel(T* __restrict__ d, int N,
-                              const int* __restrict__ n_arr) {
+//
+// MASKED: `src` is the actor head's delay matrix as it stands (garbage
+// outside link cells) and `adj` the adjacency mask; the load applies
+// i==j ? 0 : (adj ? src : +inf) itself and the result goes to `d`, a fresh
+// uninitialised output, pad cells included (+inf, 0 on the diagonal) —
+// what the unmasked kernel computes in place from a prepared clone, bit for
+// bit, without the five (B,N,N) passes that prepare it.  Unmasked: src == d.
+template <typename T, bool MASKED>
+__global__ void fw_lds_kernel(const T* src, const bool* __restrict__ adj,
+                              T* d, int N, const int* __restrict__ n_arr) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     T* s = reinterpret_cast<T*>(smem_raw);
     T* D = d + (size_t)blockIdx.x * N * N;
+    const T* S = src + (size_t)blockIdx.x * N * N;
+    const bool* A = MASKED ? adj + (size_t)blockIdx.x * N * N : nullptr;
     const int n = n_arr ? n_arr[blockIdx.x] : N;
     const int tid = threadIdx.x;
     const int nt = blockDim.x;
@@ -42,7 +51,14 @@ __global__ void fw_lds_kernel(T* __restrict__ d, int N,
     const int ns = (sizeof(T) == 4) ? ((n + 3) & ~3) : n;
     for (int c = tid; c < n * ns; c += nt) {
         const int r = c / ns, j = c % ns;
-        s[c] = j < n ? D[(size_t)r * N + j] : (T)INFINITY;
+        T v = (T)INFINITY;
+        if (j < n) {
+            const size_t g = (size_t)r * N + j;
+            if (!MASKED) v = S[g];
+            else if (r == j) v = (T)0;
+            else if (A[g]) v = S[g];
+        }
+        s[c] = v;
     }
     __syncthreads();
     // thread layout: each of 32 lanes per half-wave owns a 4-column group,
@@ -81,8 +97,16 @@ __global__ void fw_lds_kernel(T* __restrict__ d, int N,
             __syncthreads();
         }
     }
-    for (int c = tid; c < n * n; c += nt)
-        D[(size_t)(c / n) * N + (c % n)] = s[(c / n) * ns + (c % n)];
+    if (MASKED) {
+        for (int c = tid; c < N * N; c += nt) {
+            const int r = c / N, j = c % N;
+            D[c] = (r < n && j < n) ? s[r * ns + j]
+                                    : (r == j ? (T)0 : (T)INFINITY);
+        }
+    } else {
+        for (int c = tid; c < n * n; c += nt)
+            D[(size_t)(c / n) * N + (c % n)] = s[(c / n) * ns + (c % n)];
+    }
 }
 
 // ---- tiled (global-memory) path for large N -------------------------------
@@ -355,8 +379,9 @@ torch::Tensor floyd_warshall_hip(torch::Tensor w,
         const int Ns = sizeof(scalar_t) == 4 ? ((N + 3) & ~3) : N;
         const size_t lds = (size_t)N * Ns * sizeof(scalar_t);
         if (lds <= LDS_LIMIT) {
-            hipLaunchKernelGGL(fw_lds_kernel<scalar_t>, dim3(B), dim3(512),
-                               lds, stream.stream(),
+            hipLaunchKernelGGL((fw_lds_kernel<scalar_t, false>), dim3(B),
+                               dim3(512), lds, stream.stream(),
+                               d.data_ptr<scalar_t>(), nullptr,
                                d.data_ptr<scalar_t>(), N, np_);
         } else if constexpr (std::is_same_v<scalar_t, float>) {
             // fp32 large-N: TILE=64 (half the fabric traffic of TILE=32,
@@ -398,4 +423,33 @@ torch::Tensor floyd_warshall_hip(torch::Tensor w,
         }
     });
     return d;
+}
+
+// APSP straight from the actor head's delay matrix: non-edges → +inf,
+// diagonal → 0 in the LDS load (see fw_lds_kernel<MASKED>).  Shapes too
+// large for the LDS kernel prepare the matrix with torch and take the tiled
+// path.
+torch::Tensor floyd_warshall_dm_hip(torch::Tensor dm, torch::Tensor adj,
+                                    c10::optional<torch::Tensor> n_arr) {
+    TORCH_CHECK(dm.is_cuda() && dm.dim() == 3 && dm.size(1) == dm.size(2),
+                "expected (B,N,N) CUDA tensor");
+    TORCH_CHECK(adj.scalar_type() == torch::kBool
+                && adj.sizes() == dm.sizes(), "adj: (B,N,N) bool expected");
+    const int B = dm.size(0), N = dm.size(1);
+    const size_t lds = (size_t)N * ((N + 3) & ~3) * sizeof(float);
+    if (dm.scalar_type() != torch::kFloat || lds > LDS_LIMIT) {
+        auto w = torch::where(adj, dm, torch::full_like(dm, INFINITY));
+        auto eye = torch::eye(N, adj.options()).unsqueeze(0);
+        return floyd_warshall_hip(
+            torch::where(eye, torch::zeros_like(w), w), n_arr);
+    }
+    dm = dm.contiguous();
+    adj = adj.contiguous();
+    auto out = torch::empty_like(dm);
+    const int* np_ = n_arr.has_value() ? n_arr->data_ptr<int>() : nullptr;
+    hipLaunchKernelGGL((fw_lds_kernel<float, true>), dim3(B), dim3(512), lds,
+                       at::cuda::getCurrentCUDAStream().stream(),
+                       dm.data_ptr<float>(), adj.data_ptr<bool>(),
+                       out.data_ptr<float>(), N, np_);
+    return out;
 }

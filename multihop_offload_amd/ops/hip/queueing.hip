@@ -218,9 +218,100 @@ __global__ void actor_head_fwd_kernel(
     }
 }
 
-// actor head backward: grad_dist (B,N,N) → δλ_ext (B,Ee)
+// ---- cotangent sources of the actor head backward ------------------------
+// The backward needs the (B,N,N) cotangent only at the cells the forward
+// wrote: both directions of every real link and the diagonal.  DenseCot
+// reads them from a dense tensor; FusedCot assembles them on the fly from
+// the critic's grad_edge and the 0.001·MSE anchor, and sums the anchor's
+// squared error on the way (engine.grad_dist_matrix without its dozen
+// (B,N,N) passes).
+struct DenseCot {
+    const float* grad_dist;                // (B,N,N)
+    DEV_INLINE float cell(int b, int N, int r, int c, int /*edge*/,
+                          float& /*sq*/, int& /*cnt*/) const {
+        return grad_dist[((size_t)b * N + r) * N + c];
+    }
+    DEV_INLINE void finish(int, float, int, float*, float*) const {}
+};
+
+struct FusedCot {
+    const float* grad_edge;                // (B,Ee)
+    const float* dm;                       // (B,N,N) valid on link+diag cells
+    const float* unit_mtx;                 // (B,N,N) meaningful where written
+    const bool* written;                   // (B,N,N)
+    float* mse_sq;                         // (B) Σ diff²
+    int* mse_cnt;                          // (B) anchor cells
+    int Ee;
+    // grad_edge[edge] + anchor(r,c); edge < 0 (a node without a compute
+    // slot) contributes the anchor alone.  unit_mtx is read only where
+    // written is set, dm only on the cells this kernel visits (the actor
+    // head leaves dm uninitialised elsewhere).
+    DEV_INLINE float cell(int b, int N, int r, int c, int edge, float& sq,
+                          int& cnt) const {
+#pragma clang fp contract(off)
+        const size_t i = ((size_t)b * N + r) * N + c;
+        float a = 0.f;
+        if (written[i]) {
+            const float d = dm[i];
+            if (isfinite(d)) {
+                const float diff = d - unit_mtx[i];
+                a = 0.001f * diff;
+                sq += diff * diff;
+                cnt += 1;
+            }
+        }
+        const float ge = edge >= 0 ? grad_edge[(size_t)b * Ee + edge] : 0.f;
+        return ge + a;
+    }
+    // one (Σ, count) pair per graph; called by every thread of the block.
+    // The two accumulators are cells of the plan's own LDS that the kernel
+    // has finished with (no static LDS on top of the plan's bytes).
+    DEV_INLINE void finish(int b, float sq, int cnt, float* free1,
+                           float* free2) const {
+        float* s_sq = free1;
+        int* s_cnt = reinterpret_cast<int*>(free2);
+        if (threadIdx.x == 0) { *s_sq = 0.f; *s_cnt = 0; }
+        __syncthreads();
+        if (cnt) { atomicAdd(s_sq, sq); atomicAdd(s_cnt, cnt); }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            mse_sq[b] = *s_sq;
+            mse_cnt[b] = *s_cnt;
+        }
+    }
+};
+
+// loss_mse = Σ_b Σ diff² / max(Σ_b count, 1), one block
+__global__ void mse_finish_kernel(const float* __restrict__ mse_sq,
+                                  const int* __restrict__ mse_cnt, int B,
+                                  float* __restrict__ out) {
+    __shared__ float s_sq[256];
+    __shared__ long long s_cnt[256];       // integer count, like torch's
+    float sq = 0.f;
+    long long cnt = 0;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        sq += mse_sq[b];
+        cnt += mse_cnt[b];
+    }
+    s_sq[threadIdx.x] = sq;
+    s_cnt[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+            s_sq[threadIdx.x] += s_sq[threadIdx.x + w];
+            s_cnt[threadIdx.x] += s_cnt[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        out[0] = s_sq[0] / (float)(s_cnt[0] > 1 ? s_cnt[0] : 1);
+}
+
+// actor head backward: cotangent on dm (dense or fused, see above) → δλ_ext
+// (B,Ee)
+template <class Cot>
 __global__ void actor_head_bwd_kernel(
-    const float* __restrict__ grad_dist,   // (B,N,N)
+    const Cot cot,
     const float* __restrict__ lam_ext,     // (B,Ee)
     const float* __restrict__ mu_hist,     // (B,(iters+1),E)
     const Tables t,                        // bw = bw_comp (B,C)
@@ -242,10 +333,11 @@ __global__ void actor_head_bwd_kernel(
     float* s2 = lds + p.s2;
     const Graph g = graph_view(t, b);
     const float* le = lam_ext + (size_t)b * Ee;
-    const float* gd = grad_dist + (size_t)b * N * N;
     const int* edg = edges + (size_t)b * E * 2;
     const long* nv = node_vedge + (size_t)b * N;
     float* out = dlam_ext + (size_t)b * Ee;
+    float sq = 0.f;                        // FusedCot's anchor error
+    int cnt = 0;
 
     for (int e = tid; e < g.Eb; e += nt) lam[e] = le[e];
     if (!p.large) {
@@ -259,7 +351,8 @@ __global__ void actor_head_bwd_kernel(
     // link part: cotangent = gd[u,v] + gd[v,u] (dm wrote both)
     for (int e = tid; e < g.Eb; e += nt) {
         const int u = edg[e * 2], v = edg[e * 2 + 1];
-        const float dd = gd[(size_t)u * N + v] + gd[(size_t)v * N + u];
+        const float dd = cot.cell(b, N, u, v, e, sq, cnt)
+            + cot.cell(b, N, v, u, e, sq, cnt);
         float dl_, dm_;
         unit_bwd(lam[e], mu_last[e], g.T, 101.0f, cap, dd, &dl_, &dm_);
         dlam[e] = dl_;
@@ -273,10 +366,12 @@ __global__ void actor_head_bwd_kernel(
     // node part: diagonal cotangent, direct (no fixed point)
     for (int n = tid; n < N; n += nt) {
         const long ve = nv[n];
+        // every diagonal cell is visited: the anchor error counts it even
+        // where there is no compute slot to hand a gradient to
+        const float dd = cot.cell(b, N, n, n, (int)ve, sq, cnt);
         if (ve >= 0) {
             float dl_, dm_;
-            unit_bwd(le[ve], g.bw[ve - E], g.T, 100.0f, cap,
-                     gd[(size_t)n * N + n], &dl_, &dm_);
+            unit_bwd(le[ve], g.bw[ve - E], g.T, 100.0f, cap, dd, &dl_, &dm_);
             out[ve] = dl_;
         }
     }
@@ -284,6 +379,8 @@ __global__ void actor_head_bwd_kernel(
     for (int e = tid; e < Ee; e += nt) {
         if (e >= E + C) out[e] = 0.f;
     }
+    // s1 / s2 were last read inside fixed_point_bwd, behind its barrier
+    cot.finish(b, sq, cnt, s1, s2);
 }
 
 }  // namespace
@@ -358,22 +455,23 @@ std::vector<torch::Tensor> actor_head_fwd_hip(
     return {dm, mu_hist};
 }
 
-torch::Tensor actor_head_bwd_hip(
-    torch::Tensor grad_dist, torch::Tensor lam_ext, torch::Tensor mu_hist,
+namespace {
+
+template <class Cot>
+torch::Tensor actor_head_bwd_launch(
+    const Cot& cot, int N, torch::Tensor lam_ext, torch::Tensor mu_hist,
     torch::Tensor conf_indptr, torch::Tensor conf_base,
     torch::Tensor conf_cols, torch::Tensor rates, torch::Tensor bw_comp,
     torch::Tensor edges, torch::Tensor node_vedge, torch::Tensor T_arr,
     torch::Tensor E_arr, long iters, double cap) {
     const int B = lam_ext.size(0), Ee = lam_ext.size(1);
     const int E = rates.size(1), C = bw_comp.size(1);
-    const int N = grad_dist.size(1);
     auto dlam = torch::zeros_like(lam_ext);
     const ActorBwdPlan p = actor_bwd_plan(E, (int)iters);
     TORCH_CHECK(p.fits, "graph too large for LDS actor head bwd");
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(actor_head_bwd_kernel, dim3(B), dim3(p.threads),
-                       p.lds_bytes, stream.stream(),
-                       grad_dist.data_ptr<float>(),
+    hipLaunchKernelGGL(actor_head_bwd_kernel<Cot>, dim3(B), dim3(p.threads),
+                       p.lds_bytes, stream.stream(), cot,
                        lam_ext.data_ptr<float>(), mu_hist.data_ptr<float>(),
                        tables(conf_indptr, conf_base, conf_cols, rates,
                               bw_comp, T_arr, E_arr),
@@ -381,6 +479,62 @@ torch::Tensor actor_head_bwd_hip(
                        dlam.data_ptr<float>(),
                        p, (float)cap, N, E, C, Ee, (int)iters);
     return dlam;
+}
+
+}  // namespace
+
+torch::Tensor actor_head_bwd_hip(
+    torch::Tensor grad_dist, torch::Tensor lam_ext, torch::Tensor mu_hist,
+    torch::Tensor conf_indptr, torch::Tensor conf_base,
+    torch::Tensor conf_cols, torch::Tensor rates, torch::Tensor bw_comp,
+    torch::Tensor edges, torch::Tensor node_vedge, torch::Tensor T_arr,
+    torch::Tensor E_arr, long iters, double cap) {
+    return actor_head_bwd_launch(
+        DenseCot{grad_dist.data_ptr<float>()}, (int)grad_dist.size(1),
+        lam_ext, mu_hist, conf_indptr, conf_base, conf_cols, rates, bw_comp,
+        edges, node_vedge, T_arr, E_arr, iters, cap);
+}
+
+// Same backward with the cotangent assembled in the kernel:
+//   link e=(u,v):  (ge[e] + a(u,v)) + (ge[e] + a(v,u))
+//   node n, slot ve:  ge[ve] + a(n,n)
+//   a(c) = written[c] && isfinite(dm[c]) ? 0.001·(dm[c] − unit_mtx[c]) : 0
+// in the association order of `grad_dist + anchor` followed by the dense
+// kernel's gd[u,v] + gd[v,u], so dλ is bit-equal to the dense route.
+// walk_eval_kernel (episode.hip, stages 3/3b) sets `written` only at
+// (u,v)/(v,u) of a routed real link and at (d,d) of a destination, i.e.
+// inside the 2·E_b + N cells visited here, so the anchor mask is covered.
+// Returns (dλ (B,Ee), loss_mse 0-dim).
+std::vector<torch::Tensor> actor_head_bwd_fused_hip(
+    torch::Tensor grad_edge, torch::Tensor dm, torch::Tensor unit_mtx,
+    torch::Tensor written, torch::Tensor lam_ext, torch::Tensor mu_hist,
+    torch::Tensor conf_indptr, torch::Tensor conf_base,
+    torch::Tensor conf_cols, torch::Tensor rates, torch::Tensor bw_comp,
+    torch::Tensor edges, torch::Tensor node_vedge, torch::Tensor T_arr,
+    torch::Tensor E_arr, long iters, double cap) {
+    const int B = lam_ext.size(0), Ee = lam_ext.size(1);
+    const int N = dm.size(1);
+    TORCH_CHECK(grad_edge.is_contiguous() && dm.is_contiguous()
+                && unit_mtx.is_contiguous() && written.is_contiguous()
+                && lam_ext.is_contiguous(), "contiguous inputs expected");
+    TORCH_CHECK(grad_edge.size(0) == B && grad_edge.size(1) == Ee
+                && dm.size(0) == B && dm.size(2) == N
+                && unit_mtx.sizes() == dm.sizes()
+                && written.sizes() == dm.sizes(), "shape mismatch");
+    auto mse_sq = torch::empty({B}, lam_ext.options());
+    auto mse_cnt = torch::empty({B}, lam_ext.options().dtype(torch::kInt));
+    auto dlam = actor_head_bwd_launch(
+        FusedCot{grad_edge.data_ptr<float>(), dm.data_ptr<float>(),
+                 unit_mtx.data_ptr<float>(), written.data_ptr<bool>(),
+                 mse_sq.data_ptr<float>(), mse_cnt.data_ptr<int>(), Ee},
+        N, lam_ext, mu_hist, conf_indptr, conf_base, conf_cols, rates,
+        bw_comp, edges, node_vedge, T_arr, E_arr, iters, cap);
+    auto loss_mse = torch::empty({}, lam_ext.options());
+    hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0,
+                       at::cuda::getCurrentCUDAStream().stream(),
+                       mse_sq.data_ptr<float>(), mse_cnt.data_ptr<int>(), B,
+                       loss_mse.data_ptr<float>());
+    return {dlam, loss_mse};
 }
 
 // Host-only: what each queueing kernel's launcher would launch with at this

@@ -40,6 +40,7 @@ setup(
                 "multihop_offload_amd/ops/hip/chebconv.hip",
                 "multihop_offload_amd/ops/hip/optimizer.hip",
                 "multihop_offload_amd/ops/hip/chebconv_large.hip",
+                "multihop_offload_amd/ops/hip/step_glue.hip",
             ],
             depends=["multihop_offload_amd/ops/hip/cheb_tiles.h",
                      "multihop_offload_amd/ops/hip/queue_model.h",
