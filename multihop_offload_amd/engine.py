@@ -63,6 +63,22 @@ class EpisodeResult:
     delay_emp: torch.Tensor      # (B, J) per-job empirical delay (nan-padded)
     loss_fn: Optional[torch.Tensor] = None      # 0-dim, on device
     loss_mse: Optional[torch.Tensor] = None
+    # the episode's decisions and routes (what ``simulate`` replays)
+    dst: Optional[torch.Tensor] = None          # (B, J) computing node
+    route_links: Optional[torch.Tensor] = None  # (B, J, H) link ids, -1 pad
+    nhop: Optional[torch.Tensor] = None         # (B, J)
+
+
+@dataclasses.dataclass
+class SimResult:
+    """Per-job outcome of the per-timeslot packet simulation of an episode's
+    routes (``EpisodeEngine.simulate``)."""
+    delay_sum: torch.Tensor      # (B, J) int64, slots over completed tasks
+    count: torch.Tensor          # (B, J) completed tasks with t0 >= warmup
+    mean_delay: torch.Tensor     # (B, J) delay_sum / count, nan where 0
+    backlog: torch.Tensor        # (B, J) arrived after warmup, not completed
+    trace: Optional[torch.Tensor] = None   # (B, T, 3) arrivals, departures,
+    #                                        tasks in network per slot
 
 
 class EpisodeEngine:
@@ -1025,10 +1041,11 @@ class EpisodeEngine:
                         self._collect_per_sample_grads()
             self.per_sample_request = False
 
-        return self._result(jobs, delay_emp, loss_fn, loss_mse)
+        return self._result(jobs, delay_emp, loss_fn, loss_mse,
+                            routes=(dst, route_links, nhop))
 
     def _result(self, jobs: JobBatch, delay_emp: torch.Tensor,
-                loss_fn=None, loss_mse=None) -> EpisodeResult:
+                loss_fn=None, loss_mse=None, routes=None) -> EpisodeResult:
         """Per-graph summary of an episode: mean delay over the real jobs,
         congested-job and job counts (one HIP launch on the native path)."""
         if self.native_glue:
@@ -1040,9 +1057,93 @@ class EpisodeEngine:
                              torch.zeros_like(delay_emp))
             tau = de.sum(1) / nj.to(self.dtype)
             congest = ((delay_emp > self.T_arr[:, None]) & jobs.mask).sum(1)
+        dst, route_links, nhop = routes or (None, None, None)
         return EpisodeResult(tau=tau, congest=congest, num_jobs=nj,
                              delay_emp=delay_emp, loss_fn=loss_fn,
-                             loss_mse=loss_mse)
+                             loss_mse=loss_mse, dst=dst,
+                             route_links=route_links, nhop=nhop)
+
+    # ----------------------------------------------- packet-level simulation
+    def draw_arrivals(self, jobs: JobBatch, T_sim: int,
+                      gen: Optional[torch.Generator] = None) -> torch.Tensor:
+        """Per-slot Poisson arrival counts (B, T_sim, J) uint8 for
+        ``simulate``, drawn on the engine's device; masked job slots are
+        zero.  Raises if a count does not fit uint8."""
+        lam = torch.where(jobs.mask, jobs.rates,
+                          torch.zeros_like(jobs.rates))
+        lam = lam[:, None, :].expand(self.B, int(T_sim), lam.shape[1])
+        arr = torch.poisson(lam.contiguous(), generator=gen)
+        if arr.numel() and float(arr.max()) > 255:
+            raise ValueError("draw_arrivals: a slot count exceeds 255 "
+                             "(uint8) — job rates too high for the "
+                             "simulator's arrival format")
+        return arr.to(torch.uint8)
+
+    def simulate(self, jobs: JobBatch, result: EpisodeResult,
+                 arrivals: torch.Tensor, warmup: int = 0,
+                 trace: bool = False) -> SimResult:
+        """Replay an episode's decisions packet by packet: the per-timeslot
+        simulator of ``sim.timeslot`` over ``result``'s routes, all B graphs
+        in one HIP launch on the GPU.  ``arrivals`` is (B, T, J) counts
+        (``draw_arrivals``).  On the CPU engine each case runs
+        ``simulate_routes`` on its own fp64 arrays, so B=1 equals
+        ``sim.timeslot.simulate``."""
+        if result.dst is None or result.route_links is None \
+                or result.nhop is None:
+            raise ValueError("simulate: the EpisodeResult carries no routes")
+        B, J = self.B, self.Jmax
+        arrivals = torch.as_tensor(arrivals, device=self.device)
+        assert arrivals.shape[0] == B and arrivals.shape[2] == J, \
+            (tuple(arrivals.shape), (B, J))
+        T_sim = arrivals.shape[1]
+        warmup = int(warmup)
+        if self.use_hip:
+            delay_sum, count, tr = ops.timeslot_sim(
+                arrivals, result.route_links, result.nhop, result.dst,
+                jobs.mask, jobs.ul, jobs.dl, self.link_rates, self.proc_bws,
+                self.k_conf_indptr, self.k_conf_base, self.k_conf_cols,
+                self.k_E_arr, self.k_N_arr, self.T_arr, warmup=warmup,
+                trace=trace)
+        else:
+            from .sim.timeslot import simulate_routes
+            if arrivals.numel() and (int(arrivals.max()) > 255
+                                     or int(arrivals.min()) < 0):
+                raise ValueError("simulate: arrival counts must lie in "
+                                 "[0, 255]")
+            delay_sum = torch.zeros(B, J, dtype=torch.int64)
+            count = torch.zeros(B, J, dtype=torch.int32)
+            tr = torch.zeros(B, T_sim, 3, dtype=torch.int32) if trace \
+                else None
+            arr_np = arrivals.cpu().numpy()
+            for b, g in enumerate(self.cases):
+                k = int(jobs.mask[b].sum())
+                assert bool(jobs.mask[b, :k].all()), "mask is a prefix"
+                out = simulate_routes(
+                    g, jobs.ul[b, :k].cpu().numpy().astype(np.float64),
+                    jobs.dl[b, :k].cpu().numpy().astype(np.float64),
+                    result.dst[b, :k].cpu().numpy(),
+                    result.route_links[b, :k].cpu().numpy(),
+                    result.nhop[b, :k].cpu().numpy(), arr_np[b][:, :k],
+                    warmup=warmup, trace=trace)
+                delay_sum[b, :k] = torch.as_tensor(out[0])
+                count[b, :k] = torch.as_tensor(out[1]).to(torch.int32)
+                if trace:
+                    for c, name in enumerate(("arrivals", "departures",
+                                              "pkts_in_network")):
+                        tr[b, :, c] = torch.as_tensor(
+                            out[2][name]).to(torch.int32)
+            delay_sum = delay_sum.to(self.device)
+            count = count.to(self.device)
+            tr = tr.to(self.device) if trace else None
+        cnt = count.to(torch.float64)
+        mean = torch.where(count > 0,
+                           delay_sum.to(torch.float64) / cnt.clamp(min=1),
+                           torch.full_like(cnt, float("nan")))
+        arrived = torch.where(jobs.mask[:, None, :], arrivals,
+                              torch.zeros_like(arrivals))[:, warmup:] \
+            .sum(1, dtype=torch.int64)
+        return SimResult(delay_sum=delay_sum, count=count, mean_delay=mean,
+                         backlog=arrived - count.to(torch.int64), trace=tr)
 
     def _collect_per_sample_grads(self):
         """Slice the per-graph dW/db partials stashed by ChebStackFn's
@@ -1080,8 +1181,8 @@ class EpisodeEngine:
             uds = torch.where((self.proc_bws > 0),
                               dproc, torch.full_like(dproc, float("inf")))
             dst, est = self.offload_decide(jobs, sp, uds)
-            _, _, delay_emp, _, _ = self._episode_eval(jobs, dst, sp)
-            return self._result(jobs, delay_emp)
+            rl, nhop, delay_emp, _, _ = self._episode_eval(jobs, dst, sp)
+            return self._result(jobs, delay_emp, routes=(dst, rl, nhop))
 
     def local_episode(self, jobs: JobBatch) -> EpisodeResult:
         """Local computing (offloading_v3.py:363-386), batched."""
@@ -1092,11 +1193,13 @@ class EpisodeEngine:
                 # the fused kernel handles src==dst routes (0 hops) directly
                 sp0 = torch.zeros(B, self.N, self.N, dtype=self.dtype,
                                   device=self.device)
-                _, _, delay_emp, _, _ = self._episode_eval(jobs, dst, sp0)
+                route_links, nhop, delay_emp, _, _ = self._episode_eval(
+                    jobs, dst, sp0)
             else:
                 route_links = torch.full((B, J, 0), -1, dtype=torch.int64,
                                          device=self.device)
                 nhop = torch.zeros(B, J, dtype=torch.int64,
                                    device=self.device)
                 delay_emp, *_ = self.evaluate(jobs, dst, route_links, nhop)
-            return self._result(jobs, delay_emp)
+            return self._result(jobs, delay_emp,
+                                routes=(dst, route_links, nhop))

@@ -25,12 +25,36 @@ from .train_batched import build_training_cases
 
 def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
              device, dtype, workers: int = 8, lam_margin: float = 0.0,
-             refine: int = 0):
+             refine: int = 0, simulate: int = 0, sim_warmup: int = 0):
     """Returns per-method aggregate {tau, congest_jobs, num_jobs} summed /
-    averaged over all (size, case, instance)."""
-    agg = {m: {"tau_sum": 0.0, "tau_n": 0, "congest": 0, "jobs": 0,
-               "ratio_sum": 0.0, "ratio_n": 0}
-           for m in ("baseline", "local", "GNN")}
+    averaged over all (size, case, instance).  ``simulate`` > 0 also replays
+    every episode's routes in the per-timeslot packet simulator for that
+    many slots (one arrival draw per job instance, shared by the methods,
+    from a generator of its own so the analytic fields do not move) and
+    adds ``sim_tau`` (task-weighted mean simulated sojourn of the tasks
+    that arrived after ``sim_warmup`` and completed), ``sim_backlog_ratio``
+    (the share of those arrivals still in the network at the end) and
+    ``sim_tasks`` (completed tasks)."""
+    def fresh():
+        return {"tau_sum": 0.0, "tau_n": 0, "congest": 0, "jobs": 0,
+                "ratio_sum": 0.0, "ratio_n": 0, "sim_delay": 0,
+                "sim_tasks": 0, "sim_backlog": 0, "sim_arrived": 0}
+
+    def fields(d, jobs_too=False):
+        out = {"tau": d["tau_sum"] / max(d["tau_n"], 1),
+               "congest_ratio": d["congest"] / max(d["jobs"], 1),
+               "latency_ratio": d["ratio_sum"] / max(d["ratio_n"], 1)}
+        if jobs_too:
+            out["jobs"] = d["jobs"]
+        if simulate:
+            out["sim_tau"] = (d["sim_delay"] / d["sim_tasks"]
+                              if d["sim_tasks"] else float("nan"))
+            out["sim_backlog_ratio"] = (d["sim_backlog"]
+                                        / max(d["sim_arrived"], 1))
+            out["sim_tasks"] = d["sim_tasks"]
+        return out
+
+    agg = {m: fresh() for m in ("baseline", "local", "GNN")}
     per_size = {}
     for n in sizes:
         cases = build_training_cases(n, cases_per_size, cases_per_size, T,
@@ -39,9 +63,9 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
                                lam_margin=lam_margin)
         gen = torch.Generator(device=device)
         gen.manual_seed(seed + n)
-        ps = {m: {"tau_sum": 0.0, "tau_n": 0, "congest": 0, "jobs": 0,
-                  "ratio_sum": 0.0, "ratio_n": 0}
-              for m in ("baseline", "local", "GNN")}
+        sim_gen = torch.Generator(device=device)
+        sim_gen.manual_seed(seed + n + 7919)
+        ps = {m: fresh() for m in ("baseline", "local", "GNN")}
         for _ in range(instances):
             jobs = engine.sample_jobs(load, gen)
             results = {
@@ -50,11 +74,16 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
                 "GNN": engine.gnn_episode(jobs, train=False,
                                           refine=refine),
             }
+            arrivals = (engine.draw_arrivals(jobs, simulate, sim_gen)
+                        if simulate else None)
             bl = results["baseline"].delay_emp
             for m, res in results.items():
                 # per-task latency ratio vs baseline (notebook cell 16)
                 r = res.delay_emp / bl
                 ok = torch.isfinite(r)
+                sim = (engine.simulate(jobs, res, arrivals,
+                                       warmup=sim_warmup)
+                       if simulate else None)
                 for d in (agg[m], ps[m]):
                     d["tau_sum"] += float(torch.nansum(res.tau))
                     d["tau_n"] += int(torch.isfinite(res.tau).sum())
@@ -62,18 +91,15 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
                     d["jobs"] += int(res.num_jobs.sum())
                     d["ratio_sum"] += float(r[ok].sum())
                     d["ratio_n"] += int(ok.sum())
+                    if sim is not None:
+                        d["sim_delay"] += int(sim.delay_sum.sum())
+                        d["sim_tasks"] += int(sim.count.sum())
+                        d["sim_backlog"] += int(sim.backlog.sum())
+                        d["sim_arrived"] += int(sim.backlog.sum()
+                                                + sim.count.sum())
         engine.check_overflow()       # strict: truncated walks void an eval
-        per_size[n] = {
-            m: {"tau": d["tau_sum"] / max(d["tau_n"], 1),
-                "congest_ratio": d["congest"] / max(d["jobs"], 1),
-                "latency_ratio": d["ratio_sum"] / max(d["ratio_n"], 1)}
-            for m, d in ps.items()}
-    summary = {
-        m: {"tau": d["tau_sum"] / max(d["tau_n"], 1),
-            "congest_ratio": d["congest"] / max(d["jobs"], 1),
-            "latency_ratio": d["ratio_sum"] / max(d["ratio_n"], 1),
-            "jobs": d["jobs"]}
-        for m, d in agg.items()}
+        per_size[n] = {m: fields(d) for m, d in ps.items()}
+    summary = {m: fields(d, jobs_too=True) for m, d in agg.items()}
     return summary, per_size
 
 
@@ -99,6 +125,13 @@ def main(argv=None):
                          "analytic delay exceeds T fall back to local and "
                          "the assignment is re-evaluated (NOT reference "
                          "semantics; reported results must say so)")
+    ap.add_argument("--simulate", type=int, default=0, metavar="T_SIM",
+                    help="also replay every episode in the per-timeslot "
+                         "packet simulator for T_SIM slots and report "
+                         "sim_tau / sim_backlog_ratio / sim_tasks next to "
+                         "the analytic fields (0 = off)")
+    ap.add_argument("--sim-warmup", type=int, default=0,
+                    help="slots whose arrivals the simulated figures skip")
     ap.add_argument("--out", type=str, default="out/eval_summary.json")
     args = ap.parse_args(argv)
 
@@ -117,7 +150,9 @@ def main(argv=None):
                                  args.instances, args.T, args.load,
                                  args.seed, device, dtype, args.workers,
                                  lam_margin=args.lam_margin,
-                                 refine=args.refine)
+                                 refine=args.refine,
+                                 simulate=args.simulate,
+                                 sim_warmup=args.sim_warmup)
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     with open(args.out, "w") as f:
         json.dump({"summary": summary, "per_size": per_size,

@@ -56,3 +56,95 @@ def floyd_warshall(w: torch.Tensor, n_arr=None) -> torch.Tensor:
         ext = _require_hip()
         return ext.floyd_warshall(w.contiguous(), n_arr)
     return torch_ref.floyd_warshall(w)
+
+
+def timeslot_lds_plan(N: int, E: int, J: int) -> dict:
+    """LDS plan of the timeslot simulator kernel for a batch of N nodes, at
+    most E links and J job slots: ``lds_bytes``, ``threads``, ``large``,
+    ``fits`` — the launcher's own plan."""
+    return dict(_require_hip().timeslot_lds_plan(int(N), int(E), int(J)))
+
+
+def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
+                 proc_bws, conf_indptr, conf_base, conf_cols, E_arr, n_arr,
+                 T_arr=None, warmup: int = 0, trace: bool = False):
+    """Batched per-timeslot packet simulation of ``sim.timeslot``.
+
+    ``arrivals`` (B,T,J) integer counts (at most 255 each; masked job slots
+    are ignored), routes as the episode kernels return them
+    (``route_links`` (B,J,H) padded -1, ``nhop``, ``dst``), the job payloads
+    and the engine's batch tables.  Returns ``(delay_sum int64 (B,J), count
+    int32 (B,J), trace int32 (B,T,3) or None)`` with the trace columns
+    (arrivals, departures, tasks in network).  GPU tensors run the HIP
+    kernel (required — no eager fallback); CPU tensors loop over
+    ``simulate_routes``."""
+    B, T, J = arrivals.shape
+    if arrivals.numel() and (int(arrivals.max()) > 255
+                             or int(arrivals.min()) < 0):
+        raise ValueError("timeslot_sim: arrival counts must lie in [0, 255]")
+    mask = mask.to(torch.bool)
+    arr = torch.where(mask[:, None, :], arrivals,
+                      torch.zeros_like(arrivals)).to(torch.uint8).contiguous()
+    if route_links.shape[2] == 0:
+        route_links = route_links.new_full((B, J, 1), -1)
+    warmup = int(warmup)
+    if warmup < 0:
+        raise ValueError("timeslot_sim: warmup must be non-negative")
+
+    if arr.is_cuda:
+        ext = _require_hip()
+        slot_off = torch.zeros(B, T + 1, dtype=torch.int32, device=arr.device)
+        slot_off[:, 1:] = arr.sum(2, dtype=torch.int64).cumsum(1)
+        pool = int(slot_off[:, -1].max()) if B else 0
+        if T_arr is None:
+            T_arr = torch.zeros(B, dtype=torch.float32, device=arr.device)
+        delay_sum, count, error, tr = ext.timeslot_sim(
+            arr, slot_off, route_links.to(torch.int32).contiguous(),
+            nhop.to(torch.int32).contiguous(),
+            dst.to(torch.int64).contiguous(), mask.contiguous(),
+            ul.to(torch.float32).contiguous(),
+            dl.to(torch.float32).contiguous(), conf_indptr, conf_base,
+            conf_cols, link_rates.to(torch.float32).contiguous(),
+            proc_bws.to(torch.float32).contiguous(),
+            T_arr.to(torch.float32).contiguous(), E_arr, n_arr, warmup,
+            pool, bool(trace))
+        if bool(error.any()):
+            bad = torch.nonzero(error).flatten().tolist()
+            raise RuntimeError(
+                "timeslot_sim: guard rail tripped (input out of range, pool "
+                f"or loop bound) in graphs {bad[:8]}, bits "
+                f"{error[bad[:8]].tolist()}")
+        return delay_sum, count, (tr if trace else None)
+
+    from types import SimpleNamespace
+
+    import numpy as np
+
+    from ..sim.timeslot import simulate_routes
+    delay_sum = torch.zeros(B, J, dtype=torch.int64)
+    count = torch.zeros(B, J, dtype=torch.int32)
+    tr = torch.zeros(B, T, 3, dtype=torch.int32) if trace else None
+    cip = conf_indptr.numpy()
+    cols = conf_cols.numpy()
+    N = proc_bws.shape[1]
+    for b in range(B):
+        Eb = int(E_arr[b])
+        lo = int(conf_base[b])
+        g = SimpleNamespace(
+            num_links=Eb, num_nodes=N, conf_indptr=cip[b, :Eb + 1],
+            conf_indices=cols[lo:lo + int(cip[b, Eb])],
+            link_rates=link_rates[b, :Eb].numpy().astype(np.float64),
+            proc_bws=proc_bws[b].numpy().astype(np.float64))
+        idx = torch.nonzero(mask[b]).flatten()
+        out = simulate_routes(
+            g, ul[b, idx].numpy().astype(np.float64),
+            dl[b, idx].numpy().astype(np.float64), dst[b, idx].numpy(),
+            route_links[b, idx].numpy(), nhop[b, idx].numpy(),
+            arr[b][:, idx].numpy(), warmup=warmup, trace=trace)
+        delay_sum[b, idx] = torch.as_tensor(out[0])
+        count[b, idx] = torch.as_tensor(out[1]).to(torch.int32)
+        if trace:
+            for k, name in enumerate(("arrivals", "departures",
+                                      "pkts_in_network")):
+                tr[b, :, k] = torch.as_tensor(out[2][name]).to(torch.int32)
+    return delay_sum, count, tr

@@ -252,3 +252,14 @@ class _FusedAdamGroup(dict):
         super().__setitem__(key, value)
         if key == "lr":
             self._opt.lr = value
+
+
+def timeslot_sim(*args, **kwargs):
+    """Batched per-timeslot packet simulation; see
+    :func:`multihop_offload_amd.ops.dispatch.timeslot_sim`."""
+    return dispatch.timeslot_sim(*args, **kwargs)
+
+
+def timeslot_lds_fits(N: int, E: int, J: int) -> bool:
+    """True when the simulator kernel's LDS plan holds this batch shape."""
+    return bool(dispatch.timeslot_lds_plan(N, E, J)["fits"])

@@ -258,4 +258,34 @@ inline WalkPlan walk_plan(int N, int E) {
         });
 }
 
+// timeslot_sim (timeslot.hip): 32-bit words, all in LDS — queue heads and
+// tails, the finished chains (head, first target, length) and the
+// per-resource job chains over the R = E + N resources, one bit per
+// resource, the busy flags, five per-job rows and four scalars.  The task
+// pool is global.  4 * (6 R + ceil(R / 32) + E + 5 J + 4) bytes.
+struct TimeslotPlan : Launch {
+    int head, tail, fhead, ftgt0, fcnt, jfirst, fmask, busy, arr, jres,
+        jnext, jnh, jdst, misc;
+};
+inline TimeslotPlan timeslot_plan(int N, int E, int J) {
+    return make_plan<TimeslotPlan>(
+        launch_threads(E, N), [=](TimeslotPlan& p, Carve& c) {
+            const size_t R = (size_t)E + N;
+            p.head = c.lds(R);
+            p.tail = c.lds(R);
+            p.fhead = c.lds(R);
+            p.ftgt0 = c.lds(R);
+            p.fcnt = c.lds(R);
+            p.jfirst = c.lds(R);
+            p.fmask = c.lds((R + 31) / 32);
+            p.busy = c.lds(E);
+            p.arr = c.lds(J);
+            p.jres = c.lds(J);
+            p.jnext = c.lds(J);
+            p.jnh = c.lds(J);
+            p.jdst = c.lds(J);
+            p.misc = c.lds(4);
+        });
+}
+
 }  // namespace qm

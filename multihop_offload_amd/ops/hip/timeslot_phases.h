@@ -1,0 +1,322 @@
+// Per-slot phases of the per-timeslot packet simulator (timeslot.hip), written
+// against one graph's state so that the same text runs as a workgroup on the
+// GPU and as plain C++ on the host (tests/host/timeslot_host.cpp calls every
+// phase for tid = 0..nt-1, one phase after the other).
+//
+// The contract is sim/timeslot.py::simulate_routes, integer for integer.
+// Resources are the Eb real links, then the N nodes; each owns a FIFO of
+// tasks threaded through `next` in the task pool.  Nothing here contains a
+// barrier: the caller separates the phases.  Order never depends on timing —
+// every queue is appended to by exactly one thread per phase (its owner,
+// r % nt == tid), and that thread walks its sources in the oracle's order.
+//
+//   init_jobs   | init_queues | then per slot t:
+//   arrive(t)   : owner of r appends slot t's new tasks bound for r (j
+//                 ascending), then snapshots busy[r]
+//   serve(t)    : owner of r drains its FIFO against the slot's capacity and
+//                 chains what it popped through `fnext` (pop order)
+//   handover(t) : owner of r walks the source resources that finished
+//                 something (a bit set, ascending) and appends the finished
+//                 tasks whose next leg is r; thread 0 writes the
+//                 trace row; slot t+1's arrival counts are staged
+//
+// Guard rails: every index read from memory is range-checked before use and
+// every loop has a bound derived from the pool capacity P; a violation sets
+// st.misc[ERR] and the caller stops stepping that graph.
+
+#pragma once
+
+#include <cstdint>
+
+#ifndef DEV_INLINE
+#define DEV_INLINE inline
+#endif
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TSIM_COUNT_ADD(p, v) atomicAdd((p), (v))   // integer count only
+#define TSIM_SET_BITS(p, v) atomicOr((p), (v))     // a set: no order in it
+#else
+#define TSIM_COUNT_ADD(p, v) (*(p) += (v))
+#define TSIM_SET_BITS(p, v) (*(p) |= (v))
+#endif
+
+namespace tsim {
+
+enum { ERR = 0, DEP = 1, INNET = 2, MISC_WORDS = 4 };
+enum {  // error bits
+    E_INPUT = 1,    // route / nhop / dst out of range
+    E_POOL = 2,     // task index or pool offset out of range
+    E_BOUND = 4,    // a loop ran past its iteration bound
+    E_TARGET = 8    // a task's next resource out of range
+};
+
+struct Case {                       // one graph, read-only
+    int Eb, n, N, J, H, T, warmup, P;
+    const int* cip;                 // (Eb+1) conflict CSR row pointers
+    const int* ccols;               // conflict CSR columns
+    const float* rates;             // (Eb) link rates
+    const float* bw;                // (N) node bandwidths
+    const unsigned char* arrivals;  // (T,J)
+    const int* slot_off;            // (T+1) exclusive prefix of slot totals
+    const int* route_links;         // (J,H), -1 padded
+    const int* nhop;                // (J)
+    const int64_t* dst;             // (J)
+    const bool* mask;               // (J)
+    const float* ul;                // (J)
+    const float* dl;                // (J)
+};
+
+struct State {                      // one graph, mutable
+    // task pool (global memory), P entries each
+    int* job;
+    int* stage;
+    int* t0;
+    int* next;                      // FIFO link
+    int* fnext;                     // finished-this-slot chain (pop order)
+    int* tgt;                       // next leg's resource
+    double* rem;
+    // per-resource / per-job words (LDS on the GPU)
+    int* head;                      // (R)
+    int* tail;                      // (R)
+    int* fhead;                     // (R)
+    int* ftgt0;                     // (R) next resource of fhead[r]
+    int* fcnt;                      // (R) length of r's finished chain
+    unsigned* fmask;                // (ceil(R/32)) bit r: fhead[r] non-empty
+    int* busy;                      // (Eb)
+    int* arr;                       // (J) staged arrival counts of the slot
+    int* jres;                      // (J) first leg's resource; -1 masked, -2 bad
+    int* jfirst;                    // (R) first job whose first leg is r
+    int* jnext;                     // (J) next job with the same first leg
+    int* jnh;                       // (J) validated nhop (0 where masked)
+    int* jdst;                      // (J) validated dst
+    int* misc;                      // (MISC_WORDS)
+    // outputs
+    long long* delay_sum;           // (J)
+    int* count;                     // (J)
+    int* trace;                     // (T,3) or null
+};
+
+DEV_INLINE int num_res(const Case& c) { return c.Eb + c.N; }
+DEV_INLINE int mask_words(int R) { return (R + 31) / 32; }
+
+// resource of leg `stage` of job j; -1 once the task has no legs left
+DEV_INLINE int leg_res(const Case& c, const State& st, int j, int stage) {
+    const int nh = st.jnh[j];
+    if (stage < nh) return c.route_links[(size_t)j * c.H + stage];
+    if (stage == nh) return c.Eb + st.jdst[j];
+    if (stage <= 2 * nh) return c.route_links[(size_t)j * c.H + 2 * nh - stage];
+    return -1;
+}
+
+DEV_INLINE double leg_units(const Case& c, const State& st, int j,
+                            int stage) {
+    return stage <= st.jnh[j] ? (double)c.ul[j] : (double)c.dl[j];
+}
+
+DEV_INLINE void stage_arrivals(const Case& c, State& st, int t, int tid,
+                               int nt) {
+    for (int j = tid; j < c.J; j += nt)
+        st.arr[j] = st.jres[j] >= 0
+            ? (int)c.arrivals[(size_t)t * c.J + j] : 0;
+}
+
+DEV_INLINE void append(State& st, int r, int q) {
+    st.next[q] = -1;
+    const int tl = st.tail[r];
+    if (tl >= 0) st.next[tl] = q; else st.head[r] = q;
+    st.tail[r] = q;
+}
+
+// ---- init, part 1: validate the jobs, first-leg table, zero the outputs --
+DEV_INLINE void init_jobs(const Case& c, State& st, int tid, int nt) {
+    if (tid == 0) {
+        int bad = 0;
+        if (c.Eb < 0 || c.n < 0 || c.n > c.N || c.P < 0 ||
+            c.slot_off[0] != 0 || c.slot_off[c.T] > c.P)
+            bad = E_INPUT;
+        st.misc[ERR] = bad;
+        st.misc[DEP] = 0;
+        st.misc[INNET] = 0;
+    }
+    for (int j = tid; j < c.J; j += nt) {
+        st.delay_sum[j] = 0;
+        st.count[j] = 0;
+        int res = -1;
+        st.jnh[j] = 0;
+        st.jdst[j] = 0;
+        if (c.mask[j]) {
+            const int nh = c.nhop[j];
+            const long long d = c.dst[j];
+            bool ok = nh >= 0 && nh <= c.H && d >= 0 && d < c.n;
+            for (int h = 0; ok && h < nh; ++h) {
+                const int l = c.route_links[(size_t)j * c.H + h];
+                ok = l >= 0 && l < c.Eb;
+            }
+            if (ok) {
+                st.jnh[j] = nh;
+                st.jdst[j] = (int)d;
+            }
+            res = ok ? leg_res(c, st, j, 0) : -2;  // -2: reported in part 2
+        }
+        st.jres[j] = res;
+    }
+}
+
+// ---- init, part 2: empty queues, per-resource job chains, slot 0 staged --
+DEV_INLINE void init_queues(const Case& c, State& st, int tid, int nt) {
+    const int R = num_res(c);
+    for (int r = tid; r < R; r += nt) {
+        st.head[r] = st.tail[r] = st.fhead[r] = st.ftgt0[r] = -1;
+        st.fcnt[r] = 0;
+        if (r < c.Eb) st.busy[r] = 0;
+        int first = -1;
+        for (int j = c.J - 1; j >= 0; --j)
+            if (st.jres[j] == r) { st.jnext[j] = first; first = j; }
+        st.jfirst[r] = first;
+    }
+    for (int j = tid; j < c.J; j += nt)
+        if (st.jres[j] == -2) st.misc[ERR] = E_INPUT;
+    if (c.T > 0) stage_arrivals(c, st, 0, tid, nt);
+}
+
+// ---- arrivals of slot t, then the busy snapshot ---------------------------
+DEV_INLINE void arrive(const Case& c, State& st, int t, int tid, int nt) {
+    const int R = num_res(c);
+    for (int w = tid; w < mask_words(R); w += nt) st.fmask[w] = 0u;
+    for (int r = tid; r < R; r += nt) {
+        int it = 0;
+        for (int j = st.jfirst[r]; j >= 0; j = st.jnext[j]) {
+            if (j >= c.J || ++it > c.J) { st.misc[ERR] = E_BOUND; break; }
+            const int k = st.arr[j];
+            if (k <= 0) continue;
+            int off = c.slot_off[t];
+            for (int i = 0; i < j; ++i) off += st.arr[i];
+            if (off < 0 || off + k > c.P) { st.misc[ERR] = E_POOL; break; }
+            const double units = leg_units(c, st, j, 0);
+            for (int i = 0; i < k; ++i) {
+                const int q = off + i;
+                st.job[q] = j;
+                st.stage[q] = 0;
+                st.t0[q] = t;
+                st.rem[q] = units;
+                append(st, r, q);
+            }
+        }
+        if (r < c.Eb) st.busy[r] = st.head[r] >= 0;
+    }
+}
+
+// ---- service: every resource drains its own FIFO --------------------------
+DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
+    const int R = num_res(c);
+    for (int r = tid; r < R; r += nt) {
+        int fh = -1, ft = -1, ftg = -1, nf = 0;
+        int q = st.head[r];
+        if (q >= 0) {
+            double cap;
+            if (r < c.Eb) {
+                int nb = 0;
+                for (int a = c.cip[r]; a < c.cip[r + 1]; ++a) {
+                    const int o = c.ccols[a];
+                    if (o < 0 || o >= c.Eb) { st.misc[ERR] = E_INPUT; break; }
+                    nb += st.busy[o];
+                }
+                cap = (double)c.rates[r] / (1.0 + (double)nb);
+            } else {
+                cap = (double)c.bw[r - c.Eb];
+            }
+            int it = 0;
+            while (cap > 0.0 && q >= 0) {
+                if (q >= c.P) { st.misc[ERR] = E_POOL; break; }
+                if (++it > c.P) { st.misc[ERR] = E_BOUND; break; }
+                double rem = st.rem[q];
+                const double served = rem < cap ? rem : cap;
+                rem -= served;
+                cap -= served;
+                if (!(rem <= 1e-12)) { st.rem[q] = rem; break; }
+                const int nq = st.next[q];
+                const int j = st.job[q];
+                if (j < 0 || j >= c.J) { st.misc[ERR] = E_POOL; break; }
+                const int stage = st.stage[q] + 1;
+                st.stage[q] = stage;
+                const int nr = leg_res(c, st, j, stage);
+                if (nr < 0) {                       // no legs left
+                    const int t0 = st.t0[q];
+                    if (t0 >= c.warmup) {
+                        st.delay_sum[j] += (long long)(t + 1 - t0);
+                        st.count[j] += 1;
+                    }
+                    TSIM_COUNT_ADD(&st.misc[DEP], 1);
+                } else if (nr >= R) {
+                    st.misc[ERR] = E_TARGET;
+                    break;
+                } else {
+                    st.tgt[q] = nr;
+                    st.rem[q] = leg_units(c, st, j, stage);
+                    st.fnext[q] = -1;
+                    if (ft >= 0) st.fnext[ft] = q; else { fh = q; ftg = nr; }
+                    ft = q;
+                    ++nf;
+                }
+                q = nq;
+            }
+            st.head[r] = q;
+            if (q < 0) st.tail[r] = -1;
+        }
+        st.fhead[r] = fh;
+        st.ftgt0[r] = ftg;
+        st.fcnt[r] = nf;
+        if (fh >= 0) TSIM_SET_BITS(&st.fmask[r >> 5], 1u << (r & 31));
+    }
+}
+
+// ---- hand-over: finished tasks join their next queue, oracle order --------
+DEV_INLINE void handover(const Case& c, State& st, int t, int tid, int nt) {
+    const int R = num_res(c);
+    for (int r = tid; r < R; r += nt) {
+        int it = 0;
+        bool stop = false;
+        // sources with something to hand over, ascending: the set bits
+        for (int w = 0; w < mask_words(R) && !stop; ++w) {
+            for (unsigned m = st.fmask[w]; m && !stop; m &= m - 1) {
+                const int s = w * 32 + __builtin_ctz(m);
+                if (s >= R) { st.misc[ERR] = E_BOUND; stop = true; break; }
+                // the chain's first task and its target are in LDS (most
+                // chains hold one task); the rest follow through the pool
+                const int n = st.fcnt[s];
+                int q = st.fhead[s], tg = st.ftgt0[s];
+                for (int i = 0; i < n; ++i) {
+                    if (q < 0 || q >= c.P) {
+                        st.misc[ERR] = E_POOL; stop = true; break;
+                    }
+                    if (++it > c.P) {
+                        st.misc[ERR] = E_BOUND; stop = true; break;
+                    }
+                    if (tg == r) append(st, r, q);
+                    if (i + 1 < n) {
+                        q = st.fnext[q];
+                        if (q < 0 || q >= c.P) {
+                            st.misc[ERR] = E_POOL; stop = true; break;
+                        }
+                        tg = st.tgt[q];
+                    }
+                }
+            }
+        }
+    }
+    if (tid == 0) {
+        const int arrived = c.slot_off[t + 1] - c.slot_off[t];
+        const int dep = st.misc[DEP];
+        st.misc[DEP] = 0;
+        st.misc[INNET] += arrived - dep;
+        if (st.trace) {
+            const int td = t + 1 < c.T ? t + 1 : c.T - 1;
+            st.trace[(size_t)t * 3 + 0] = arrived;
+            st.trace[(size_t)td * 3 + 1] += dep;
+            st.trace[(size_t)t * 3 + 2] = st.misc[INNET];
+        }
+    }
+    if (t + 1 < c.T) stage_arrivals(c, st, t + 1, tid, nt);
+}
+
+}  // namespace tsim

@@ -40,34 +40,54 @@ class _Task:
         self.done_at = -1
 
 
-def simulate(g: CaseGraph, jobs: JobInstance, flows: List[Flow],
-             T: int = 2000, seed: int = 0, warmup: int = 0,
-             trace: bool = False):
-    """Returns (mean_delay_per_job (J,), completed_counts (J,)); with
-    ``trace=True`` also a dict of per-slot totals (arrivals, sink
-    departures, packets in network — the reference ``plot_metrics``
-    series, offloading_v3.py:588-607)."""
+def draw_arrivals(jobs: JobInstance, T: int, seed: int) -> np.ndarray:
+    """The (T, J) per-slot arrival counts ``simulate(seed=seed)`` draws
+    inline: one ``RandomState(seed)`` stream, slot-major, job-minor."""
     rng = np.random.RandomState(seed)
-    E, J = g.num_links, jobs.num_jobs
+    rates = np.asarray(jobs.rates, dtype=np.float64)
+    return rng.poisson(rates, size=(int(T), len(rates)))
+
+
+def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
+                    warmup: int = 0, trace: bool = False):
+    """The simulator loop over explicit routes — the contract of the batched
+    HIP kernel (ops/hip/timeslot.hip), which reproduces it integer for
+    integer.
+
+    ``g`` supplies ``num_links``, ``num_nodes``, ``conf_indptr``,
+    ``conf_indices``, ``link_rates`` and ``proc_bws``; ``route_links`` is
+    (J, H) with job j's links in its first ``nhop[j]`` columns; ``arrivals``
+    is (T, J) integer counts.  Returns ``(delay_sum int64 (J,), count int64
+    (J,))`` over the tasks that arrived at ``t0 >= warmup`` and completed,
+    plus the trace dict with ``trace=True``."""
+    arrivals = np.asarray(arrivals)
+    T, J = arrivals.shape
+    E, N = int(g.num_links), int(g.num_nodes)
+    route_links = np.asarray(route_links).reshape(J, -1)
+    conf_indptr = np.asarray(g.conf_indptr)
+    conf_indices = np.asarray(g.conf_indices)
+    link_rates = np.asarray(g.link_rates)
+    proc_bws = np.asarray(g.proc_bws)
 
     # per-job leg sequence: [("link", l, ul)...] , ("node", dst, ul),
     # [("link", l, dl)... reversed]
     legs = []
-    env = AdhocCloudEnv(g)
-    for j, f in enumerate(flows):
-        links = env.route_links(f) if f.src != f.dst else np.empty(0, int)
-        seq = [("link", int(l), float(jobs.ul[j])) for l in links]
-        seq.append(("node", int(f.dst), float(jobs.ul[j])))
-        seq += [("link", int(l), float(jobs.dl[j])) for l in links[::-1]]
+    for j in range(J):
+        links = route_links[j, :int(nhop[j])]
+        seq = [("link", int(l), float(ul[j])) for l in links]
+        seq.append(("node", int(dst[j]), float(ul[j])))
+        seq += [("link", int(l), float(dl[j])) for l in links[::-1]]
         legs.append(seq)
 
     link_q: List[List[_Task]] = [[] for _ in range(E)]
-    node_q: List[List[_Task]] = [[] for _ in range(g.num_nodes)]
-    delays = [[] for _ in range(J)]
+    node_q: List[List[_Task]] = [[] for _ in range(N)]
+    delay_sum = np.zeros(J, dtype=np.int64)
+    count = np.zeros(J, dtype=np.int64)
     tr_arr = np.zeros(T, dtype=np.int64)
     tr_dep = np.zeros(T, dtype=np.int64)
     tr_net = np.zeros(T, dtype=np.int64)
     in_network = 0
+    rows = np.repeat(np.arange(E), np.diff(conf_indptr[:E + 1]))
 
     def enqueue(task: _Task, t: int):
         while task.stage < len(legs[task.job]):
@@ -77,12 +97,13 @@ def simulate(g: CaseGraph, jobs: JobInstance, flows: List[Flow],
             return
         task.done_at = t
         if task.t0 >= warmup:
-            delays[task.job].append(t - task.t0)
+            delay_sum[task.job] += t - task.t0
+            count[task.job] += 1
 
     for t in range(T):
         # arrivals
         for j in range(J):
-            for _ in range(rng.poisson(jobs.rates[j])):
+            for _ in range(int(arrivals[t, j])):
                 task = _Task(j, t)
                 tr_arr[t] += 1
                 in_network += 1
@@ -91,15 +112,14 @@ def simulate(g: CaseGraph, jobs: JobInstance, flows: List[Flow],
                     in_network -= 1
                     tr_dep[t] += 1
         # link service with contention sharing
-        busy = np.array([1 if q else 0 for q in link_q])
+        busy = np.array([1 if q else 0 for q in link_q], dtype=np.int64)
         nb_busy = np.zeros(E)
-        rows = np.repeat(np.arange(E), np.diff(g.conf_indptr))
-        np.add.at(nb_busy, rows, busy[g.conf_indices])
+        np.add.at(nb_busy, rows, busy[conf_indices])
         finished = []
         for l in range(E):
             if not link_q[l]:
                 continue
-            cap = g.link_rates[l] / (1.0 + nb_busy[l])
+            cap = link_rates[l] / (1.0 + nb_busy[l])
             while cap > 0 and link_q[l]:
                 head = link_q[l][0]
                 served = min(cap, head.remaining)
@@ -111,10 +131,10 @@ def simulate(g: CaseGraph, jobs: JobInstance, flows: List[Flow],
                     finished.append(head)
                 else:
                     break
-        for n in range(g.num_nodes):
+        for n in range(N):
             if not node_q[n]:
                 continue
-            cap = g.proc_bws[n]
+            cap = proc_bws[n]
             while cap > 0 and node_q[n]:
                 head = node_q[n][0]
                 served = min(cap, head.remaining)
@@ -133,9 +153,77 @@ def simulate(g: CaseGraph, jobs: JobInstance, flows: List[Flow],
                 tr_dep[min(t + 1, T - 1)] += 1
         tr_net[t] = in_network
 
-    mean_delay = np.array([np.mean(d) if d else np.nan for d in delays])
-    counts = np.array([len(d) for d in delays])
     if trace:
-        return mean_delay, counts, {"arrivals": tr_arr, "departures": tr_dep,
-                                    "pkts_in_network": tr_net}
-    return mean_delay, counts
+        return delay_sum, count, {"arrivals": tr_arr, "departures": tr_dep,
+                                  "pkts_in_network": tr_net}
+    return delay_sum, count
+
+
+def simulate(g: CaseGraph, jobs: JobInstance, flows: List[Flow],
+             T: int = 2000, seed: int = 0, warmup: int = 0,
+             trace: bool = False, arrivals=None):
+    """Returns (mean_delay_per_job (J,), completed_counts (J,)); with
+    ``trace=True`` also a dict of per-slot totals (arrivals, sink
+    departures, packets in network — the reference ``plot_metrics``
+    series, offloading_v3.py:588-607).  ``arrivals`` ((T, J) counts)
+    replaces the seeded Poisson draws; ``draw_arrivals(jobs, T, seed)`` is
+    the stream ``seed`` alone would give."""
+    J = jobs.num_jobs
+    if arrivals is None:
+        arrivals = draw_arrivals(jobs, T, seed)
+    arrivals = np.asarray(arrivals)
+    assert arrivals.shape == (T, J), (arrivals.shape, (T, J))
+
+    env = AdhocCloudEnv(g)
+    routes = [env.route_links(f) if f.src != f.dst else np.empty(0, int)
+              for f in flows]
+    nhop = np.array([len(r) for r in routes], dtype=np.int64)
+    route_links = -np.ones((J, max(int(nhop.max()) if J else 0, 1)),
+                           dtype=np.int64)
+    for j, r in enumerate(routes):
+        route_links[j, :len(r)] = r
+    dst = np.array([f.dst for f in flows], dtype=np.int64)
+
+    out = simulate_routes(g, jobs.ul, jobs.dl, dst, route_links, nhop,
+                          arrivals, warmup=warmup, trace=trace)
+    delay_sum, count = out[0], out[1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean_delay = np.where(count > 0, delay_sum / np.maximum(count, 1),
+                              np.nan)
+    if trace:
+        return mean_delay, count, out[2]
+    return mean_delay, count
+
+
+def dump_case(path, g, ul, dl, dst, route_links, nhop, arrivals,
+              warmup: int = 0):
+    """Flat binary dump of one ``simulate_routes`` case for the stand-alone
+    host program (tests/host/timeslot_host.cpp): nine int32 header words
+    ``E N J H T warmup P nconf 0``, then conf_indptr (E+1) int32,
+    conf_indices int32, link_rates (E) fp32, proc_bws (N) fp32, arrivals
+    (T,J) uint8, slot_off (T+1) int32, route_links (J,H) int32, nhop (J)
+    int32, dst (J) int64, ul (J) fp32, dl (J) fp32.  The rates are rounded
+    to fp32, as the kernel holds them."""
+    arrivals = np.asarray(arrivals)
+    T, J = arrivals.shape
+    assert arrivals.min(initial=0) >= 0 and arrivals.max(initial=0) <= 255
+    E, N = int(g.num_links), int(g.num_nodes)
+    rl = np.asarray(route_links, dtype=np.int32).reshape(J, -1)
+    if rl.shape[1] == 0:
+        rl = -np.ones((J, 1), dtype=np.int32)
+    slot_off = np.zeros(T + 1, dtype=np.int32)
+    slot_off[1:] = np.cumsum(arrivals.sum(axis=1))
+    cip = np.asarray(g.conf_indptr, dtype=np.int32)[:E + 1]
+    cols = np.asarray(g.conf_indices, dtype=np.int32)[:cip[-1]]
+    head = np.array([E, N, J, rl.shape[1], T, warmup, max(int(slot_off[-1]), 1),
+                     len(cols), 0], dtype=np.int32)
+    with open(path, "wb") as f:
+        for a in (head, cip, cols,
+                  np.asarray(g.link_rates, dtype=np.float32)[:E],
+                  np.asarray(g.proc_bws, dtype=np.float32)[:N],
+                  arrivals.astype(np.uint8), slot_off, rl,
+                  np.asarray(nhop, dtype=np.int32),
+                  np.asarray(dst, dtype=np.int64),
+                  np.asarray(ul, dtype=np.float32),
+                  np.asarray(dl, dtype=np.float32)):
+            f.write(np.ascontiguousarray(a).tobytes())

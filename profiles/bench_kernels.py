@@ -5,6 +5,12 @@ episode step in isolation with hip events, at the flagship config
 
 Run on an MI355X:  python profiles/bench_kernels.py [--config flagship|er1000]
 Output: one JSON line per (config, stage) with mean µs over the timed reps.
+
+``--config timeslot`` times the per-timeslot packet simulator instead
+(B=256, N=100, load 0.15, T=1000): the bare kernel launch, the whole
+``EpisodeEngine.simulate`` call, and the Python ``simulate_routes`` on a few
+of the same instances on this host's CPU (whose outputs must equal the
+kernel's), with the ratio per batch.
 """
 import argparse
 import json
@@ -141,12 +147,93 @@ def bench_config(name, nodes, batch, gtype, distinct, reps):
     return out
 
 
+def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
+                   py_instances=4):
+    import time
+    from types import SimpleNamespace
+
+    import numpy as np
+
+    from multihop_offload_amd.engine import EpisodeEngine
+    from multihop_offload_amd.models.chebconv import ChebConvStack
+    from multihop_offload_amd.harness.train_batched import build_training_cases
+    from multihop_offload_amd.ops import dispatch
+    from multihop_offload_amd.sim.timeslot import simulate_routes
+
+    cases = build_training_cases(nodes, batch, 16, 1000, 7, gtype="ba",
+                                 workers=8)
+    model = ChebConvStack(K=2, dtype=torch.float32, seed=3)
+    eng = EpisodeEngine(cases, model, device="cuda", dtype=torch.float32)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(0)
+    jobs = eng.sample_jobs(load, gen)
+    res = eng.baseline_episode(jobs)
+    arr = eng.draw_arrivals(jobs, T_sim, gen)
+    sim = eng.simulate(jobs, res, arr)
+    tasks = int(arr.sum())
+
+    # the bare launch: the wrapper's prefix sums and error read left out
+    ext = dispatch.require_hip()
+    slot_off = torch.zeros(eng.B, T_sim + 1, dtype=torch.int32,
+                           device="cuda")
+    slot_off[:, 1:] = arr.sum(2, dtype=torch.int64).cumsum(1)
+    pool = int(slot_off[:, -1].max())
+    args = (arr, slot_off, res.route_links.contiguous(),
+            res.nhop.contiguous(), res.dst.contiguous(), jobs.mask,
+            jobs.ul.contiguous(), jobs.dl.contiguous(), eng.k_conf_indptr,
+            eng.k_conf_base, eng.k_conf_cols, eng.link_rates.contiguous(),
+            eng.proc_bws.contiguous(), eng.T_arr.contiguous(), eng.k_E_arr,
+            eng.k_N_arr, 0, pool, False)
+    out = ext.timeslot_sim(*args)
+    assert not bool(out[2].any())
+    assert torch.equal(out[0], sim.delay_sum)
+    kernel_us = timeit(lambda: ext.timeslot_sim(*args), reps)
+    call_us = timeit(lambda: eng.simulate(jobs, res, arr), reps)
+
+    # the Python simulator on the first instances, same host, same inputs
+    f64 = lambda x: x.cpu().numpy().astype(np.float64)   # noqa: E731
+    t_py = 0.0
+    for b in range(py_instances):
+        g = cases[b]
+        k = int(jobs.mask[b].sum())
+        view = SimpleNamespace(
+            num_links=g.num_links, num_nodes=g.num_nodes,
+            conf_indptr=g.conf_indptr, conf_indices=g.conf_indices,
+            link_rates=f64(eng.link_rates[b, :g.num_links]),
+            proc_bws=f64(eng.proc_bws[b]))
+        a = (view, f64(jobs.ul[b, :k]), f64(jobs.dl[b, :k]),
+             res.dst[b, :k].cpu().numpy(),
+             res.route_links[b, :k].cpu().numpy(),
+             res.nhop[b, :k].cpu().numpy(), arr[b][:, :k].cpu().numpy())
+        t0 = time.perf_counter()
+        ds, ct = simulate_routes(*a)
+        t_py += time.perf_counter() - t0
+        assert np.array_equal(ds, sim.delay_sum[b, :k].cpu().numpy())
+        assert np.array_equal(ct, sim.count[b, :k].cpu().numpy())
+    py_s = t_py / py_instances
+    plan = dispatch.timeslot_lds_plan(eng.N, eng.E, eng.Jmax)
+    print(json.dumps({
+        "config": f"timeslot_b{batch}_n{nodes}", "stage": "timeslot_sim",
+        "B": eng.B, "N": eng.N, "E": eng.E, "J": eng.Jmax, "T": T_sim,
+        "load": load, "tasks": tasks, "pool": pool,
+        "lds_bytes": plan["lds_bytes"], "threads": plan["threads"],
+        "kernel_us": round(kernel_us, 1), "simulate_call_us": round(call_us, 1),
+        "python_s_per_instance": round(py_s, 4),
+        "python_instances_timed": py_instances,
+        "python_s_per_batch": round(py_s * eng.B, 2),
+        "ratio_python_over_kernel": round(py_s * eng.B / (kernel_us * 1e-6)),
+        "ratio_python_over_call": round(py_s * eng.B / (call_us * 1e-6)),
+        "outputs_equal_python": True}), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="both",
-                    choices=["flagship", "er1000", "both"])
+                    choices=["flagship", "er1000", "both", "timeslot"])
     ap.add_argument("--reps", type=int, default=50)
     args = ap.parse_args()
+    if args.config == "timeslot":
+        bench_timeslot(reps=args.reps)
     if args.config in ("flagship", "both"):
         bench_config("flagship_b1024_n110", 110, 1024, "ba", 16, args.reps)
     if args.config in ("er1000", "both"):

@@ -41,9 +41,11 @@ setup(
                 "multihop_offload_amd/ops/hip/optimizer.hip",
                 "multihop_offload_amd/ops/hip/chebconv_large.hip",
                 "multihop_offload_amd/ops/hip/step_glue.hip",
+                "multihop_offload_amd/ops/hip/timeslot.hip",
             ],
             depends=["multihop_offload_amd/ops/hip/cheb_tiles.h",
                      "multihop_offload_amd/ops/hip/queue_model.h",
+                     "multihop_offload_amd/ops/hip/timeslot_phases.h",
                      "multihop_offload_amd/ops/hip/gfx950.h"],
             extra_compile_args={
                 "cxx": ["-O3"],
