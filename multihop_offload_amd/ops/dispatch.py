@@ -58,6 +58,15 @@ def floyd_warshall(w: torch.Tensor, n_arr=None) -> torch.Tensor:
     return torch_ref.floyd_warshall(w)
 
 
+def queue_csr_force_global(on: bool) -> None:
+    """Make every later launch of the queueing kernels (critic, actor head,
+    walk_eval) read the conflict CSR from global memory instead of staging
+    it in LDS (``False`` restores the per-workgroup decision).  A host-side
+    switch for before/after timings and the staged-vs-global tests; the
+    results are bit-equal either way."""
+    _require_hip().queue_csr_force_global(bool(on))
+
+
 def timeslot_lds_plan(N: int, E: int, J: int) -> dict:
     """LDS plan of the timeslot simulator kernel for a batch of N nodes, at
     most E links and J job slots: ``lds_bytes``, ``threads``, ``large``,

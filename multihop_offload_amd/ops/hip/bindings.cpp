@@ -47,6 +47,10 @@ std::vector<torch::Tensor> actor_head_bwd_fused_hip(
 torch::Tensor floyd_warshall_dm_hip(torch::Tensor dm, torch::Tensor adj,
                                     c10::optional<torch::Tensor> n_arr);
 py::dict queue_lds_plan(long N, long E, long Ee, long iters);
+py::dict queue_csr_stage(long N, long E, long Ee, long iters);
+long queue_csr_bytes(long Eb, long nnz);
+void queue_csr_force_global(bool on);
+long queue_csr_set_budget(long bytes);
 
 // timeslot.hip
 std::vector<torch::Tensor> timeslot_sim_hip(
@@ -128,6 +132,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("episode_summary", &episode_summary_hip);
     m.def("jobs_from_draws", &jobs_from_draws_hip);
     m.def("queue_lds_plan", &queue_lds_plan);
+    m.def("queue_csr_stage", &queue_csr_stage);
+    m.def("queue_csr_bytes", &queue_csr_bytes);
+    m.def("queue_csr_force_global", &queue_csr_force_global);
+    m.def("queue_csr_set_budget", &queue_csr_set_budget);
     m.def("timeslot_sim", &timeslot_sim_hip);
     m.def("timeslot_lds_plan", &timeslot_lds_plan);
     m.def("cheb_fwd", &cheb_fwd_hip);

@@ -189,7 +189,8 @@ __global__ void walk_eval_kernel(
     unsigned long long* __restrict__ upack,  // (B,N,N) scratch
     int* __restrict__ overflow,          // (B) out
     const int* __restrict__ n_arr,       // (B) real node counts (padding)
-    const qm::WalkPlan p, int N, int E, int J, int H, int fp_iters) {
+    const qm::WalkPlan p, int stage_budget, int N, int E, int J, int H,
+    int fp_iters) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* lds = reinterpret_cast<float*>(smem_raw);
     float* lam = lds + p.lam;
@@ -211,6 +212,10 @@ __global__ void walk_eval_kernel(
     // runs on the real extent only (ragged-E batches, pad_to mixed-N)
     const int Eb = g.Eb;
     const int nb_ = n_arr[b];
+    // ends on a barrier when it stages; the one below covers the rest
+    const qm::Csr csr = qm::stage_csr(
+        g.cip, g.rates, g.ccols, Eb, smem_raw + qm::stage_align(p.lds_bytes),
+        stage_budget, tid, nt);
 
     for (int e = tid; e < Eb; e += nt) lam[e] = 0.0f;
     for (int n = tid; n < nb_; n += nt) sload[n] = 0.0f;
@@ -259,8 +264,7 @@ __global__ void walk_eval_kernel(
 
     // ---- stage 2: contention fixed point (offloading_v3.py:500-506) ------
     // only the last iterate is needed: row stride 0 keeps no history
-    qm::fixed_point_fwd(lam, g.rates, g.cip, g.ccols, mu, busy, Eb, 0,
-                        fp_iters, tid, nt);
+    qm::fixed_point_fwd(csr, lam, mu, busy, Eb, 0, fp_iters, tid, nt);
 
     // ---- stage 3: per-job empirical delays (offloading_v3.py:522-549) ----
     const int* edg = edges + (size_t)b * E * 2;
@@ -359,8 +363,9 @@ std::vector<torch::Tensor> walk_eval_hip(
     const qm::WalkPlan p = qm::walk_plan(N, E);
     TORCH_CHECK(p.fits, "graph too large for LDS walk_eval");
     auto stream = at::cuda::getCurrentCUDAStream();
+    const int budget = qm::stage_budget(p);
     hipLaunchKernelGGL(walk_eval_kernel, dim3(B), dim3(p.threads),
-                       p.lds_bytes, stream.stream(),
+                       qm::launch_lds_bytes(p, budget), stream.stream(),
                        sp.data_ptr<float>(), src.data_ptr<long>(),
                        dst.data_ptr<long>(), mask.data_ptr<bool>(),
                        rate.data_ptr<float>(), ul.data_ptr<float>(),
@@ -375,7 +380,7 @@ std::vector<torch::Tensor> walk_eval_hip(
                        unit_mtx.data_ptr<float>(), written.data_ptr<bool>(),
                        reinterpret_cast<unsigned long long*>(
                            upack.data_ptr<long>()),
-                       overflow.data_ptr<int>(), n_arr.data_ptr<int>(), p, N, E, J, (int)H,
-                       (int)fp_iters);
+                       overflow.data_ptr<int>(), n_arr.data_ptr<int>(), p,
+                       budget, N, E, J, (int)H, (int)fp_iters);
     return {route_links, nhop, delay_emp, unit_mtx, written, overflow};
 }

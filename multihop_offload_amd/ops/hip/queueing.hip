@@ -47,6 +47,7 @@ __global__ void critic_kernel(
     float* __restrict__ g_dlam,            // (B,Ee) scratch (prezeroed)
     const CriticPlan p,
     float cap,                             // delay clamp (0 = off)
+    int stage_budget,                      // CSR staging bytes (0 = none)
     int E, int C, int Ee, int J, int H, int iters) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* lds = reinterpret_cast<float*>(smem_raw);
@@ -66,6 +67,9 @@ __global__ void critic_kernel(
     float* s3 = lds + p.s3;
     __shared__ float loss_acc;
     const Graph g = graph_view(t, b);
+    const Csr csr = stage_csr(g.cip, g.rates, g.ccols, g.Eb,
+                              smem_raw + stage_align(p.lds_bytes),
+                              stage_budget, tid, nt);
 
     for (int e = tid; e < Ee; e += nt) {
         lam_e[e] = 0.f;
@@ -91,8 +95,7 @@ __global__ void critic_kernel(
     __syncthreads();
 
     // ---- fixed point + unit delays ---------------------------------------
-    fixed_point_fwd(lam_e, g.rates, g.cip, g.ccols, hist, s1, g.Eb, E, iters,
-                    tid, nt);
+    fixed_point_fwd(csr, lam_e, hist, s1, g.Eb, E, iters, tid, nt);
     const float* mu_last = hist + (size_t)iters * E;
     for (int e = tid; e < g.Eb; e += nt)
         unit[e] = unit_fwd(lam_e[e], mu_last[e], g.T, 101.0f, cap);
@@ -136,8 +139,8 @@ __global__ void critic_kernel(
         dlam[E + k] += dl_;                        // bw is constant
     }
     __syncthreads();
-    fixed_point_bwd(lam_e, g.rates, g.cip, g.ccols, hist, s2 /*dmu*/,
-                    s1 /*dnb*/, s3 /*dbusy*/, dlam, g.Eb, E, iters, tid, nt);
+    fixed_point_bwd(csr, lam_e, hist, s2 /*dmu*/, s1 /*dnb*/, s3 /*dbusy*/,
+                    dlam, g.Eb, E, iters, tid, nt);
     __syncthreads();
 
     // ---- grad_routes prefix scan → grad_edge -----------------------------
@@ -179,8 +182,8 @@ __global__ void actor_head_fwd_kernel(
     const long* __restrict__ node_vedge,   // (B,N)
     float* __restrict__ dm,                // (B,N,N) out (prezeroed)
     float* __restrict__ mu_hist_out,       // (B,(iters+1),E) out
-    const ActorFwdPlan p, float cap, int N, int E, int C, int Ee,
-    int iters) {
+    const ActorFwdPlan p, float cap, int stage_budget, int N, int E, int C,
+    int Ee, int iters) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* lds = reinterpret_cast<float*>(smem_raw);
     const int b = blockIdx.x;
@@ -196,9 +199,11 @@ __global__ void actor_head_fwd_kernel(
     float* dmb = dm + (size_t)b * N * N;
 
     for (int e = tid; e < g.Eb; e += nt) lam[e] = le[e];
+    const Csr csr = stage_csr(g.cip, g.rates, g.ccols, g.Eb,
+                              smem_raw + stage_align(p.lds_bytes),
+                              stage_budget, tid, nt);
     __syncthreads();
-    fixed_point_fwd(lam, g.rates, g.cip, g.ccols, hist, busy, g.Eb, E, iters,
-                    tid, nt);
+    fixed_point_fwd(csr, lam, hist, busy, g.Eb, E, iters, tid, nt);
     const float* mu_last = hist + (size_t)iters * E;
     for (int e = tid; e < g.Eb; e += nt) {
         const float d = unit_fwd(lam[e], mu_last[e], g.T, 101.0f, cap);
@@ -318,8 +323,8 @@ __global__ void actor_head_bwd_kernel(
     const int* __restrict__ edges,
     const long* __restrict__ node_vedge,
     float* __restrict__ dlam_ext,          // (B,Ee) out
-    const ActorBwdPlan p, float cap, int N, int E, int C, int Ee,
-    int iters) {
+    const ActorBwdPlan p, float cap, int stage_budget, int N, int E, int C,
+    int Ee, int iters) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* lds = reinterpret_cast<float*>(smem_raw);
     const int b = blockIdx.x;
@@ -345,6 +350,9 @@ __global__ void actor_head_bwd_kernel(
         for (size_t i = tid; i < (size_t)(iters + 1) * E; i += nt)
             h[i] = hg[i];
     }
+    const Csr csr = stage_csr(g.cip, g.rates, g.ccols, g.Eb,
+                              smem_raw + stage_align(p.lds_bytes),
+                              stage_budget, tid, nt);
     __syncthreads();
     const float* mu_last = hist + (size_t)iters * E;
 
@@ -359,8 +367,8 @@ __global__ void actor_head_bwd_kernel(
         dmu[e] = dm_;
     }
     __syncthreads();
-    fixed_point_bwd(lam, g.rates, g.cip, g.ccols, hist, dmu, s1, s2, dlam,
-                    g.Eb, E, iters, tid, nt);
+    fixed_point_bwd(csr, lam, hist, dmu, s1, s2, dlam, g.Eb, E, iters, tid,
+                    nt);
 
     for (int e = tid; e < E; e += nt) out[e] = e < g.Eb ? dlam[e] : 0.f;
     // node part: diagonal cotangent, direct (no fixed point)
@@ -413,8 +421,9 @@ std::vector<torch::Tensor> critic_hip(
         grad_edge = torch::empty({B, (long)Ee}, rates.options());
     }
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(critic_kernel, dim3(B), dim3(p.threads), p.lds_bytes,
-                       stream.stream(),
+    const int budget = stage_budget(p);
+    hipLaunchKernelGGL(critic_kernel, dim3(B), dim3(p.threads),
+                       launch_lds_bytes(p, budget), stream.stream(),
                        route_links.data_ptr<int>(), nhop.data_ptr<int>(),
                        vedge_dst.data_ptr<long>(), mask.data_ptr<bool>(),
                        rate.data_ptr<float>(), ul.data_ptr<float>(),
@@ -423,7 +432,7 @@ std::vector<torch::Tensor> critic_hip(
                               bw_comp, T_arr, E_arr),
                        grad_edge.data_ptr<float>(), loss.data_ptr<float>(),
                        g_hist.data_ptr<float>(), g_dunit.data_ptr<float>(),
-                       g_dlam.data_ptr<float>(), p, (float)cap,
+                       g_dlam.data_ptr<float>(), p, (float)cap, budget,
                        E, C, (int)Ee, J, H, (int)iters);
     return {grad_edge, loss};
 }
@@ -444,14 +453,15 @@ std::vector<torch::Tensor> actor_head_fwd_hip(
     const ActorFwdPlan p = actor_fwd_plan(E, (int)iters);
     TORCH_CHECK(p.fits, "graph too large for LDS actor head");
     auto stream = at::cuda::getCurrentCUDAStream();
+    const int budget = stage_budget(p);
     hipLaunchKernelGGL(actor_head_fwd_kernel, dim3(B), dim3(p.threads),
-                       p.lds_bytes, stream.stream(),
+                       launch_lds_bytes(p, budget), stream.stream(),
                        lam_ext.data_ptr<float>(),
                        tables(conf_indptr, conf_base, conf_cols, rates,
                               bw_comp, T_arr, E_arr),
                        edges.data_ptr<int>(), node_vedge.data_ptr<long>(),
                        dm.data_ptr<float>(), mu_hist.data_ptr<float>(),
-                       p, (float)cap, (int)N, E, C, Ee, (int)iters);
+                       p, (float)cap, budget, (int)N, E, C, Ee, (int)iters);
     return {dm, mu_hist};
 }
 
@@ -470,14 +480,15 @@ torch::Tensor actor_head_bwd_launch(
     const ActorBwdPlan p = actor_bwd_plan(E, (int)iters);
     TORCH_CHECK(p.fits, "graph too large for LDS actor head bwd");
     auto stream = at::cuda::getCurrentCUDAStream();
+    const int budget = stage_budget(p);
     hipLaunchKernelGGL(actor_head_bwd_kernel<Cot>, dim3(B), dim3(p.threads),
-                       p.lds_bytes, stream.stream(), cot,
+                       launch_lds_bytes(p, budget), stream.stream(), cot,
                        lam_ext.data_ptr<float>(), mu_hist.data_ptr<float>(),
                        tables(conf_indptr, conf_base, conf_cols, rates,
                               bw_comp, T_arr, E_arr),
                        edges.data_ptr<int>(), node_vedge.data_ptr<long>(),
                        dlam.data_ptr<float>(),
-                       p, (float)cap, N, E, C, Ee, (int)iters);
+                       p, (float)cap, budget, N, E, C, Ee, (int)iters);
     return dlam;
 }
 
@@ -551,4 +562,37 @@ py::dict queue_lds_plan(long N, long E, long Ee, long iters) {
         "actor_head_fwd"_a = row(actor_fwd_plan((int)E, (int)iters)),
         "actor_head_bwd"_a = row(actor_bwd_plan((int)E, (int)iters)),
         "walk_eval"_a = row(walk_plan((int)N, (int)E)));
+}
+
+// Host-only: the CSR staging area each launcher adds to its plan's bytes at
+// this shape, with the current setting (0: the launch reads the conflict CSR
+// from global memory).  Inside a launch a workgroup stages its graph's CSR
+// when queue_csr_bytes(E_b, nnz_b) is within that budget and E_b fits 16
+// bits.
+py::dict queue_csr_stage(long N, long E, long Ee, long iters) {
+    using namespace pybind11::literals;
+    auto row = [](const Launch& l) {
+        return py::dict("budget_bytes"_a = stage_budget(l));
+    };
+    return py::dict(
+        "critic"_a = row(critic_plan((int)E, (int)Ee, (int)iters)),
+        "actor_head_fwd"_a = row(actor_fwd_plan((int)E, (int)iters)),
+        "actor_head_bwd"_a = row(actor_bwd_plan((int)E, (int)iters)),
+        "walk_eval"_a = row(walk_plan((int)N, (int)E)));
+}
+
+long queue_csr_bytes(long Eb, long nnz) {
+    return Eb <= STAGE_MAX_E ? (long)stage_bytes(Eb, nnz) : -1;
+}
+
+// force every later launch onto the global-memory CSR (before/after timings,
+// staged-vs-global tests)
+void queue_csr_force_global(bool on) { stage_force_global = on; }
+
+// staging bytes per workgroup of later launches; negative restores the
+// default.  Returns the previous setting.
+long queue_csr_set_budget(long bytes) {
+    const long prev = stage_budget_setting;
+    stage_budget_setting = bytes < 0 ? STAGE_BUDGET_DEFAULT : (int)bytes;
+    return prev;
 }

@@ -11,6 +11,13 @@ Output: one JSON line per (config, stage) with mean µs over the timed reps.
 ``EpisodeEngine.simulate`` call, and the Python ``simulate_routes`` on a few
 of the same instances on this host's CPU (whose outputs must equal the
 kernel's), with the ratio per batch.
+
+``--config fixedpoint`` times the three kernels that are little else than
+the contention fixed point (actor_head_fwd, actor_head_bwd, critic) on the
+benchmark's own batch (BA-100, seed 100, B=256 and B=1024) at fp_iters 1
+and 10 — the slope is the cost of one iteration — with the conflict CSR
+staged in LDS at each ``--budgets`` value and forced to global memory.  On a
+build without the staging switch it times the kernels as they are.
 """
 import argparse
 import json
@@ -226,12 +233,102 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
         "outputs_equal_python": True}), flush=True)
 
 
+def bench_fixedpoint(batches=(256, 1024), budgets=(-1,), reps=200):
+    import numpy as np
+
+    from multihop_offload_amd.engine import EpisodeEngine
+    from multihop_offload_amd.models.chebconv import ChebConvStack
+    from multihop_offload_amd.harness.train_batched import build_training_cases
+    from multihop_offload_amd.ops import dispatch
+
+    ext = dispatch.require_hip()
+    has_switch = hasattr(ext, "queue_csr_force_global")
+    modes = [("as_built", None)]
+    if has_switch:
+        modes = [(f"staged_{b}" if b >= 0 else "staged_default", b)
+                 for b in budgets] + [("global", None)]
+    for batch in batches:
+        # bench.py's cases: 100 nodes, 16 distinct BA graphs, T=1000, seed 100
+        cases = build_training_cases(100, batch, 16, 1000, 100, gtype="ba",
+                                     workers=8)
+        nnz = [int(g.conf_indptr[g.num_links]) for g in cases]
+        deg = np.concatenate([np.diff(g.conf_indptr[:g.num_links + 1])
+                              for g in cases])
+        print(json.dumps({
+            "config": "fixedpoint", "B": batch, "conf_nnz_min": min(nnz),
+            "conf_nnz_max": max(nnz), "E_max": max(g.num_links for g in cases),
+            "row_degree_mean": round(float(deg.mean()), 2),
+            "row_degree_max": int(deg.max()),
+            "stage_bytes_max": (max(ext.queue_csr_bytes(g.num_links, n)
+                                    for g, n in zip(cases, nnz))
+                                if has_switch else None)}), flush=True)
+        for iters in (1, 10):
+            model = ChebConvStack(K=2, dtype=torch.float32, seed=3)
+            eng = EpisodeEngine(cases, model, device="cuda",
+                                dtype=torch.float32, fp_iters=iters)
+            gen = torch.Generator(device="cuda")
+            gen.manual_seed(0)
+            jobs = eng.sample_jobs(0.15, gen)
+            with torch.no_grad():
+                dm, *_ = eng.actor_forward(jobs)
+                sp = eng.apsp(dm)
+                uds = torch.diagonal(dm, dim1=1, dim2=2)
+                dst, _ = eng.offload_decide(jobs, sp, uds)
+                rl, nhop, *_ = eng._episode_eval(jobs, dst, sp)
+            tables = (eng.k_conf_indptr, eng.k_conf_base, eng.k_conf_cols,
+                      eng.link_rates.contiguous(), eng.bw_comp.contiguous(),
+                      eng.k_edges, eng.node_vedge, eng.T_arr.contiguous(),
+                      eng.k_E_arr)
+            lam = (torch.rand(eng.B, eng.Ee, device="cuda", generator=gen)
+                   * 5.0).contiguous()
+            vedge_dst = eng.node_vedge.gather(1, dst).contiguous()
+            fwd = lambda: ext.actor_head_fwd(     # noqa: E731
+                lam, *tables, eng.N, iters, 0.0)
+            dmk, hist = fwd()
+            gd = torch.randn_like(dmk)
+            bwd = lambda: ext.actor_head_bwd(     # noqa: E731
+                gd, lam, hist, *tables, iters, 0.0)
+            crit = lambda: ext.critic(            # noqa: E731
+                rl.contiguous(), nhop.contiguous(), vedge_dst, jobs.mask,
+                jobs.rates.contiguous(), jobs.ul.contiguous(),
+                jobs.dl.contiguous(), eng.k_conf_indptr, eng.k_conf_base,
+                eng.k_conf_cols, eng.link_rates.contiguous(),
+                eng.bw_comp.contiguous(), eng.k_E_arr,
+                eng.T_arr.contiguous(), eng.Ee, iters, 0.0)
+            walk = lambda: eng._episode_eval(jobs, dst, sp)   # noqa: E731
+            for mode, budget in modes:
+                if has_switch:
+                    ext.queue_csr_force_global(mode == "global")
+                    ext.queue_csr_set_budget(-1 if budget is None else budget)
+                row = {"config": "fixedpoint", "B": batch, "fp_iters": iters,
+                       "mode": mode}
+                if has_switch:
+                    row["budget_bytes"] = ext.queue_csr_stage(
+                        eng.N, eng.E, eng.Ee, iters)["critic"]["budget_bytes"]
+                for name, fn in (("actor_head_fwd", fwd),
+                                 ("actor_head_bwd", bwd), ("critic", crit),
+                                 ("walk_eval", walk)):
+                    row[name + "_us"] = round(timeit(fn, reps, 20), 1)
+                print(json.dumps(row), flush=True)
+            if has_switch:
+                ext.queue_csr_force_global(False)
+                ext.queue_csr_set_budget(-1)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="both",
-                    choices=["flagship", "er1000", "both", "timeslot"])
+                    choices=["flagship", "er1000", "both", "timeslot",
+                             "fixedpoint"])
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--budgets", type=str, default="-1",
+                    help="fixedpoint: staging budgets in bytes, comma-"
+                         "separated (-1 = the built-in default)")
     args = ap.parse_args()
+    if args.config == "fixedpoint":
+        bench_fixedpoint(budgets=tuple(int(b) for b in
+                                       args.budgets.split(",")),
+                         reps=max(args.reps, 100))
     if args.config == "timeslot":
         bench_timeslot(reps=args.reps)
     if args.config in ("flagship", "both"):
