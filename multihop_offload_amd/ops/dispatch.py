@@ -58,6 +58,15 @@ def floyd_warshall(w: torch.Tensor, n_arr=None) -> torch.Tensor:
     return torch_ref.floyd_warshall(w)
 
 
+def fw_force_inplace(on: bool) -> None:
+    """Make every later Floyd–Warshall launch take the in-place LDS kernel
+    instead of the register-resident one that serves fp32 up to N = 128
+    (``False`` restores the choice by shape).  A host-side switch for
+    before/after timings and the register-vs-in-place tests; the results are
+    bit-equal either way."""
+    _require_hip().fw_force_inplace(bool(on))
+
+
 def queue_csr_force_global(on: bool) -> None:
     """Make every later launch of the queueing kernels (critic, actor head,
     walk_eval) read the conflict CSR from global memory instead of staging

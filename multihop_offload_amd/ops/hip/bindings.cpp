@@ -46,6 +46,8 @@ std::vector<torch::Tensor> actor_head_bwd_fused_hip(
     torch::Tensor E_arr, long iters, double cap);
 torch::Tensor floyd_warshall_dm_hip(torch::Tensor dm, torch::Tensor adj,
                                     c10::optional<torch::Tensor> n_arr);
+void fw_force_inplace(bool on);
+long fw_register_rows(long N);
 py::dict queue_lds_plan(long N, long E, long Ee, long iters);
 py::dict queue_csr_stage(long N, long E, long Ee, long iters);
 long queue_csr_bytes(long Eb, long nnz);
@@ -126,6 +128,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("actor_head_bwd", &actor_head_bwd_hip);
     m.def("actor_head_bwd_fused", &actor_head_bwd_fused_hip);
     m.def("floyd_warshall_dm", &floyd_warshall_dm_hip);
+    m.def("fw_force_inplace", &fw_force_inplace);
+    m.def("fw_register_rows", &fw_register_rows);
     m.def("cheb_pack_params", &cheb_pack_params_hip);
     m.def("cheb_reduce_grads", &cheb_reduce_grads_hip);
     m.def("cheb_features", &cheb_features_hip);

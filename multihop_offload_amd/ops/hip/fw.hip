@@ -1,7 +1,9 @@
 // Batched all-pairs shortest paths (min-plus Floyd–Warshall) for gfx950.
 //
-// Design (MI355X-first): one workgroup per graph, the whole N×N distance
-// matrix resident in LDS (160 KiB/CU ⇒ N ≤ 200 at fp32).  The k-loop runs
+// Design (MI355X-first): one workgroup per graph.  fp32 up to N = 128 keeps
+// the matrix in registers with only the pivot row and column in LDS
+// (fw_reg_kernel); above that, and for fp64, the whole N×N distance matrix
+// is resident in LDS (160 KiB/CU ⇒ N ≤ 200 at fp32, fw_lds_kernel).  The k-loop runs
 // entirely on-chip with one barrier per k; a batch of B graphs fills the
 // 256 CUs with B workgroups.  In-place updates are safe: row k and column k
 // cannot improve through k itself (d[k][k] = 0), so no thread writes the
@@ -17,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+
+#include <type_traits>
 
 #include "gfx950.h"
 
@@ -107,6 +111,206 @@ __global__ void fw_lds_kernel(const T* src, const bool* __restrict__ adj,
         for (int c = tid; c < n * n; c += nt)
             D[(size_t)(c / n) * N + (c % n)] = s[(c / n) * ns + (c % n)];
     }
+}
+
+// ---- register-resident path, fp32, N ≤ FWR_MAX_N --------------------------
+// Only row k and column k of the matrix are read by threads other than a
+// cell's owner, so the cells live in registers: thread (tr, tc) of a
+// ceil(n/RT) × ceil(n/4) grid owns the RT×4 block at (tr·RT, tc·4), and LDS
+// holds just the pivot row and pivot column, double-buffered.  Iteration k
+// reads buffer k&1 (one float4 of row k, RT broadcast values of column k)
+// and relaxes the block, and the owners of row k+1 and column k+1 write
+// them to the other buffer: one barrier per pivot.  Row k+1 and column k+1
+// have then seen pivots 0…k, which is what fw_lds_kernel reads in place,
+// and the arithmetic per cell is the same fminf(cur, dik + dkj) in the same
+// order (fw_min below), so the result is bit-identical.  Load/store
+// conventions, MASKED and n_arr are those of fw_lds_kernel.  RT is chosen
+// by N so that the thread grid fits 512 lanes and nearly fills them
+// (N=100: 5×4 blocks, 500 lanes).
+constexpr int FWR_THREADS = 512;
+constexpr int FWR_MAX_N = 128;
+constexpr int FWR_COL_SLOTS = 256;
+
+// rows per thread for an N×N matrix; 0: not covered
+constexpr int fw_reg_rows(int N) {
+    return N <= 64 ? 2 : N <= 88 ? 4 : N <= 100 ? 5 : N <= 119 ? 7
+         : N <= FWR_MAX_N ? 8 : 0;
+}
+constexpr bool fw_reg_fits(int N) {
+    const int rt = fw_reg_rows(N);
+    return ((N + 3) / 4) * ((N + rt - 1) / rt) <= FWR_THREADS;
+}
+// the thread grid grows with n, so the largest N of each bucket decides
+static_assert(fw_reg_fits(64) && fw_reg_fits(88) && fw_reg_fits(100)
+              && fw_reg_fits(119) && fw_reg_fits(128),
+              "fw_reg_kernel: thread grid exceeds the workgroup");
+
+// fminf of two canonical values: the v_min_f32 that fminf compiles to,
+// without the v_max_f32 x, x the compiler puts in front of it for every
+// operand it cannot prove canonical (here: every cell, each pivot — a third
+// of the loop's vector instructions).  The sums pair up in v_pk_add_f32.
+typedef float float2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float fw_min(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+template <int RT, bool MASKED>
+__global__ __launch_bounds__(FWR_THREADS)
+void fw_reg_kernel(const float* src, const bool* __restrict__ adj, float* d,
+                   int N, const int* __restrict__ n_arr) {
+    // column-buffer slots per row group: a float4 multiple, so the RT
+    // values of a thread's rows read as one or two ds_read_b128
+    constexpr int CS = RT <= 4 ? 4 : 8;
+    static_assert((FWR_MAX_N + RT - 1) / RT * CS <= FWR_COL_SLOTS, "colb");
+    __shared__ __attribute__((aligned(16))) float rowb[2][FWR_MAX_N];
+    __shared__ __attribute__((aligned(16))) float colb[2][FWR_COL_SLOTS];
+    float* D = d + (size_t)blockIdx.x * N * N;
+    const float* S = src + (size_t)blockIdx.x * N * N;
+    const bool* A = MASKED ? adj + (size_t)blockIdx.x * N * N : nullptr;
+    const int n = n_arr ? min(max(n_arr[blockIdx.x], 0), N) : N;
+    const int tid = threadIdx.x;
+    const int TC = max((n + 3) >> 2, 1);
+    const int tr = tid / TC, tc = tid - tr * TC;
+    const int r0 = tr * RT, c0 = tc * 4;
+    const bool active = r0 < n;
+
+    // cells are canonicalised once here (a signalling NaN is quieted, as
+    // fminf does on every call); every later value is the result of an add
+    // or a min and canonical already
+    float c[RT][4];
+#pragma unroll
+    for (int q = 0; q < RT; ++q)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int r = r0 + q, j = c0 + p;
+            float v = INFINITY;
+            if (active && r < n && j < n) {
+                const size_t g = (size_t)r * N + j;
+                if (!MASKED) v = S[g];
+                else if (r == j) v = 0.f;
+                else if (A[g]) v = S[g];
+            }
+            c[q][p] = __builtin_canonicalizef(v);
+        }
+
+    // Pivot k = kb + P, kb a multiple of L = lcm(RT, 4): which of a thread's
+    // rows is row k+1 (QN) and which of its columns is column k+1 (PN) are
+    // then compile-time, so publishing them indexes no register dynamically.
+    // The owners of row k+1 relax and publish it before the block (those
+    // four cells are relaxed again with the block: same operands, same
+    // bits), and the half of the block that holds column k+1 goes first, so
+    // both LDS writes are under way while the rest is relaxed.
+    constexpr int L = RT % 4 == 0 ? RT : RT % 2 == 0 ? 2 * RT : 4 * RT;
+    auto relax_half = [&](auto hc, const float4& rk, const float* ck) {
+        constexpr int H = decltype(hc)::value;
+        const float2_t r2 = H == 0 ? float2_t{rk.x, rk.y}
+                                   : float2_t{rk.z, rk.w};
+#pragma unroll
+        for (int q = 0; q < RT; ++q) {
+            const float2_t dik = {ck[q], ck[q]};
+            const float2_t alt = dik + r2;
+            c[q][2 * H] = fw_min(c[q][2 * H], alt.x);
+            c[q][2 * H + 1] = fw_min(c[q][2 * H + 1], alt.y);
+        }
+    };
+    auto pivot = [&](int kb, int rgb, int cgb, auto pc) {
+        constexpr int P = decltype(pc)::value;
+        constexpr int buf = P & 1;                  // k & 1: kb is even
+        constexpr int QN = (P + 1) % RT, PN = (P + 1) % 4;
+        const bool more = kb + P + 1 < n;           // block-uniform
+        if (active) {
+            const float4 rk =
+                *reinterpret_cast<const float4*>(&rowb[buf][c0]);
+            float ck[CS];
+#pragma unroll
+            for (int q = 0; q < CS; q += 4) {
+                const float4 t = *reinterpret_cast<const float4*>(
+                    &colb[buf][tr * CS + q]);
+                ck[q] = t.x; ck[q + 1] = t.y;
+                ck[q + 2] = t.z; ck[q + 3] = t.w;
+            }
+            if (more && tr == rgb + (P + 1) / RT) {
+                const float4 v = {fw_min(c[QN][0], ck[QN] + rk.x),
+                                  fw_min(c[QN][1], ck[QN] + rk.y),
+                                  fw_min(c[QN][2], ck[QN] + rk.z),
+                                  fw_min(c[QN][3], ck[QN] + rk.w)};
+                *reinterpret_cast<float4*>(&rowb[buf ^ 1][c0]) = v;
+            }
+            relax_half(std::integral_constant<int, PN / 2>{}, rk, ck);
+            if (more && tc == cgb + (P + 1) / 4) {
+#pragma unroll
+                for (int q = 0; q < RT; ++q)
+                    colb[buf ^ 1][tr * CS + q] = c[q][PN];
+            }
+            relax_half(std::integral_constant<int, 1 - PN / 2>{}, rk, ck);
+        }
+        __syncthreads();
+    };
+    // pivots kb + P … kb + L − 1, stopping at n
+    auto pivots = [&](auto self, int kb, int rgb, int cgb, auto pc) -> void {
+        constexpr int P = decltype(pc)::value;
+        pivot(kb, rgb, cgb, pc);
+        if constexpr (P + 1 < L) {
+            if (kb + P + 1 < n)
+                self(self, kb, rgb, cgb, std::integral_constant<int, P + 1>{});
+        }
+    };
+
+    if (active && n > 0) {                          // row 0 and column 0
+        if (tr == 0)
+            *reinterpret_cast<float4*>(&rowb[0][c0]) =
+                float4{c[0][0], c[0][1], c[0][2], c[0][3]};
+        if (tc == 0) {
+#pragma unroll
+            for (int q = 0; q < RT; ++q) colb[0][tr * CS + q] = c[q][0];
+        }
+    }
+    __syncthreads();
+    for (int kb = 0, rgb = 0, cgb = 0; kb < n;      // n is block-uniform
+         kb += L, rgb += L / RT, cgb += L / 4)
+        pivots(pivots, kb, rgb, cgb, std::integral_constant<int, 0>{});
+
+    if (active) {
+#pragma unroll
+        for (int q = 0; q < RT; ++q)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int r = r0 + q, j = c0 + p;
+                if (r < n && j < n) D[(size_t)r * N + j] = c[q][p];
+            }
+    }
+    if (MASKED && n < N) {
+        for (int e = tid; e < N * N; e += FWR_THREADS) {
+            const int r = e / N, j = e % N;
+            if (r >= n || j >= n) D[e] = r == j ? 0.f : INFINITY;
+        }
+    }
+}
+
+// fw_force_inplace(true): every later launch takes fw_lds_kernel (before/
+// after timings, register-vs-in-place tests); a captured graph keeps what
+// its launches were given at capture.
+bool fw_inplace_forced = false;
+
+// Launch fw_reg_kernel if it covers N and is not switched off.
+template <bool MASKED>
+bool fw_reg_launch(const float* src, const bool* adj, float* d, int B, int N,
+                   const int* n_arr, hipStream_t stream) {
+    if (fw_inplace_forced || B == 0 || N == 0) return false;
+#define FW_REG_CASE(RT)                                                     \
+    case RT:                                                                \
+        hipLaunchKernelGGL((fw_reg_kernel<RT, MASKED>), dim3(B),            \
+                           dim3(FWR_THREADS), 0, stream, src, adj, d, N,    \
+                           n_arr);                                          \
+        return true;
+    switch (fw_reg_rows(N)) {
+        FW_REG_CASE(2) FW_REG_CASE(4) FW_REG_CASE(5) FW_REG_CASE(7)
+        FW_REG_CASE(8)
+        default: return false;
+    }
+#undef FW_REG_CASE
 }
 
 // ---- tiled (global-memory) path for large N -------------------------------
@@ -378,7 +582,13 @@ torch::Tensor floyd_warshall_hip(torch::Tensor w,
     AT_DISPATCH_FLOATING_TYPES(d.scalar_type(), "fw", [&] {
         const int Ns = sizeof(scalar_t) == 4 ? ((N + 3) & ~3) : N;
         const size_t lds = (size_t)N * Ns * sizeof(scalar_t);
-        if (lds <= LDS_LIMIT) {
+        bool in_registers = false;
+        if constexpr (std::is_same_v<scalar_t, float>)
+            in_registers = fw_reg_launch<false>(
+                d.data_ptr<float>(), nullptr, d.data_ptr<float>(), B, N, np_,
+                stream.stream());
+        if (in_registers) {
+        } else if (lds <= LDS_LIMIT) {
             hipLaunchKernelGGL((fw_lds_kernel<scalar_t, false>), dim3(B),
                                dim3(512), lds, stream.stream(),
                                d.data_ptr<scalar_t>(), nullptr,
@@ -447,9 +657,22 @@ torch::Tensor floyd_warshall_dm_hip(torch::Tensor dm, torch::Tensor adj,
     adj = adj.contiguous();
     auto out = torch::empty_like(dm);
     const int* np_ = n_arr.has_value() ? n_arr->data_ptr<int>() : nullptr;
-    hipLaunchKernelGGL((fw_lds_kernel<float, true>), dim3(B), dim3(512), lds,
-                       at::cuda::getCurrentCUDAStream().stream(),
-                       dm.data_ptr<float>(), adj.data_ptr<bool>(),
-                       out.data_ptr<float>(), N, np_);
+    auto stream = at::cuda::getCurrentCUDAStream().stream();
+    if (!fw_reg_launch<true>(dm.data_ptr<float>(), adj.data_ptr<bool>(),
+                             out.data_ptr<float>(), B, N, np_, stream))
+        hipLaunchKernelGGL((fw_lds_kernel<float, true>), dim3(B), dim3(512),
+                           lds, stream, dm.data_ptr<float>(),
+                           adj.data_ptr<bool>(), out.data_ptr<float>(), N,
+                           np_);
     return out;
+}
+
+void fw_force_inplace(bool on) { fw_inplace_forced = on; }
+
+// rows per thread of the register kernel that serves fp32 (B,N,N) input;
+// 0: N is outside its range (or it is switched off) and fw_lds_kernel or
+// the tiled path runs
+long fw_register_rows(long N) {
+    return fw_inplace_forced || N < 1 || N > FWR_MAX_N ? 0
+                                                        : fw_reg_rows((int)N);
 }

@@ -18,6 +18,10 @@ benchmark's own batch (BA-100, seed 100, B=256 and B=1024) at fp_iters 1
 and 10 — the slope is the cost of one iteration — with the conflict CSR
 staged in LDS at each ``--budgets`` value and forced to global memory.  On a
 build without the staging switch it times the kernels as they are.
+
+``--config apsp`` times the Floyd–Warshall launch of the step (``eng.apsp``)
+on the same batch and on the mixed 20–110 engine, register-resident kernel
+against the in-place LDS kernel (``fw_force_inplace``).
 """
 import argparse
 import json
@@ -315,11 +319,68 @@ def bench_fixedpoint(batches=(256, 1024), budgets=(-1,), reps=200):
                 ext.queue_csr_set_budget(-1)
 
 
+def bench_apsp(batches=(256, 1024), reps=200):
+    """``eng.apsp`` (one floyd_warshall_dm launch plus its output
+    allocation) on the benchmark's batch and on the mixed 20–110 engine
+    (10 sizes padded to 110, ``n_arr``), with the register-resident kernel
+    and forced onto the in-place LDS kernel.  On a build without the switch
+    it times the kernel as it is."""
+    from multihop_offload_amd.engine import EpisodeEngine
+    from multihop_offload_amd.models.chebconv import ChebConvStack
+    from multihop_offload_amd.harness.train_batched import build_training_cases
+    from multihop_offload_amd.ops import dispatch
+
+    ext = dispatch.require_hip()
+    has_switch = hasattr(ext, "fw_force_inplace")
+    modes = ["registers", "inplace"] if has_switch else ["as_built"]
+
+    def batch_cases(kind, batch):
+        if kind == "bench":
+            return build_training_cases(100, batch, 16, 1000, 100,
+                                        gtype="ba", workers=8)
+        sizes = list(range(20, 111, 10))
+        cases = []
+        for n in sizes:
+            cases += [c.pad_to(110) for c in build_training_cases(
+                n, max(batch // len(sizes), 8), 16, 1000, 100 + 17 * n,
+                gtype="ba", workers=8)]
+        return cases
+
+    for kind in ("bench", "mixed_20_110"):
+        for batch in batches:
+            model = ChebConvStack(K=2, dtype=torch.float32, seed=3)
+            eng = EpisodeEngine(batch_cases(kind, batch), model,
+                                device="cuda", dtype=torch.float32)
+            gen = torch.Generator(device="cuda")
+            gen.manual_seed(0)
+            jobs = eng.sample_jobs(0.15, gen)
+            with torch.no_grad():
+                dm, *_ = eng.actor_forward(jobs)
+            dm = dm.detach()
+            row = {"config": "apsp", "batch": kind, "B": eng.B, "N": eng.N,
+                   "padded": bool(eng._padded)}
+            outs = []
+            for mode in modes:
+                if has_switch:
+                    ext.fw_force_inplace(mode == "inplace")
+                    row["rows_per_thread"] = max(
+                        row.get("rows_per_thread", 0),
+                        ext.fw_register_rows(eng.N))
+                outs.append(eng.apsp(dm))
+                row[mode + "_us"] = round(
+                    timeit(lambda: eng.apsp(dm), reps, 20), 1)
+            if has_switch:
+                ext.fw_force_inplace(False)
+                row["bit_equal"] = bool(torch.equal(
+                    outs[0].view(torch.int32), outs[1].view(torch.int32)))
+            print(json.dumps(row), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="both",
                     choices=["flagship", "er1000", "both", "timeslot",
-                             "fixedpoint"])
+                             "fixedpoint", "apsp"])
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--budgets", type=str, default="-1",
                     help="fixedpoint: staging budgets in bytes, comma-"
@@ -329,6 +390,8 @@ if __name__ == "__main__":
         bench_fixedpoint(budgets=tuple(int(b) for b in
                                        args.budgets.split(",")),
                          reps=max(args.reps, 100))
+    if args.config == "apsp":
+        bench_apsp(reps=max(args.reps, 200))
     if args.config == "timeslot":
         bench_timeslot(reps=args.reps)
     if args.config in ("flagship", "both"):
