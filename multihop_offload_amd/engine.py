@@ -69,6 +69,100 @@ class EpisodeResult:
     nhop: Optional[torch.Tensor] = None         # (B, J)
 
 
+def hist_percentile(hist: torch.Tensor, dmax: torch.Tensor,
+                    q: float) -> torch.Tensor:
+    """Upper bound on the q-quantile of the sojourns behind a delay
+    histogram (``sim.timeslot.delay_bin`` bins along the last dimension):
+    the upper edge of the first bin whose cumulative count reaches
+    ``max(1, ceil(q * total))``, capped at the largest sojourn ``dmax``;
+    nan where the histogram is empty.  Exact below 16 slots, at most 12.5 %
+    over above."""
+    from .sim.timeslot import delay_bin_upper
+    hist = hist.to(torch.int64)
+    total = hist.sum(-1)
+    need = torch.ceil(q * total.to(torch.float64)).to(torch.int64) \
+        .clamp(min=1)
+    k = (hist.cumsum(-1) >= need[..., None]).to(torch.int8).argmax(-1)
+    edges = torch.tensor([delay_bin_upper(i) for i in range(hist.shape[-1])],
+                         dtype=torch.int64, device=hist.device)
+    got = torch.minimum(edges[k], dmax.to(torch.int64)).to(torch.float64)
+    return torch.where(total > 0, got, torch.full_like(got, float("nan")))
+
+
+@dataclasses.dataclass
+class SimStats:
+    """Integer statistics of one ``EpisodeEngine.simulate(stats=True)`` run
+    (definitions: ``sim.timeslot.simulate_routes``).  Per-resource tensors
+    are (B, E + N): link l at column l, node v at column E + v."""
+    delay_max: torch.Tensor      # (B, J) int32
+    late: torch.Tensor           # (B, J) int32, sojourn > late_after
+    delay_hist: torch.Tensor     # (B, J, NB) int32
+    stuck: torch.Tensor          # (B, J) int32, == SimResult.backlog
+    stuck_age: torch.Tensor      # (B, J) int64
+    qlen_sum: torch.Tensor       # (B, E + N) int64
+    qlen_max: torch.Tensor       # (B, E + N) int32
+    busy_slots: torch.Tensor     # (B, E + N) int32
+    nb_sum: torch.Tensor         # (B, E + N) int64, zero on nodes
+    delay_sum: torch.Tensor      # (B, J) int64, as in SimResult
+    count: torch.Tensor          # (B, J) int32, as in SimResult
+    late_after: torch.Tensor     # (B,) int32
+    num_links: int               # E, the column of node 0
+    T_sim: int
+    warmup: int
+
+    def _scope(self, x: torch.Tensor, per: str, how: str = "sum"):
+        """Reduce a (B, J, ...) per-job tensor over the scope ``per``."""
+        if per == "job":
+            return x
+        if per not in ("graph", "all"):
+            raise ValueError("per: 'graph', 'job' or 'all'")
+        dims = (1,) if per == "graph" else (0, 1)
+        return x.amax(dims) if how == "max" else x.sum(dims)
+
+    @staticmethod
+    def _ratio(num, den):
+        num, den = num.to(torch.float64), den.to(torch.float64)
+        return torch.where(den > 0, num / den.clamp(min=1),
+                           torch.full_like(den, float("nan")))
+
+    def percentile(self, q: float, per: str = "graph") -> torch.Tensor:
+        """Upper bound on the q-quantile (q in [0, 1]) of the counted
+        sojourns, histograms merged over the scope (``hist_percentile``)."""
+        return hist_percentile(
+            self._scope(self.delay_hist.to(torch.int64), per),
+            self._scope(self.delay_max, per, "max"), q)
+
+    def late_ratio(self, per: str = "graph") -> torch.Tensor:
+        """Share of the counted tasks later than ``late_after``."""
+        return self._ratio(self._scope(self.late.to(torch.int64), per),
+                           self._scope(self.count.to(torch.int64), per))
+
+    def censored_mean_delay(self, per: str = "graph") -> torch.Tensor:
+        """``(delay_sum + stuck_age) / (count + stuck)``: a lower bound on
+        the mean sojourn that does not drop the tasks still in the
+        network."""
+        return self._ratio(
+            self._scope(self.delay_sum + self.stuck_age, per),
+            self._scope((self.count + self.stuck).to(torch.int64), per))
+
+    def utilization(self) -> torch.Tensor:
+        """(B, E + N) share of the sampled slots with a non-empty FIFO."""
+        return self.busy_slots.to(torch.float64) \
+            / max(self.T_sim - self.warmup, 1)
+
+    def mean_qlen(self) -> torch.Tensor:
+        """(B, E + N) mean FIFO length over the sampled slots."""
+        return self.qlen_sum.to(torch.float64) \
+            / max(self.T_sim - self.warmup, 1)
+
+    def mean_contention(self) -> torch.Tensor:
+        """(B, E) mean number of busy conflicting links a link saw in its
+        own busy slots — the simulated ``sum busy`` of the fixed point's
+        ``rate / (1 + sum busy)``; nan where the link was never busy."""
+        E = self.num_links
+        return self._ratio(self.nb_sum[:, :E], self.busy_slots[:, :E])
+
+
 @dataclasses.dataclass
 class SimResult:
     """Per-job outcome of the per-timeslot packet simulation of an episode's
@@ -79,6 +173,7 @@ class SimResult:
     backlog: torch.Tensor        # (B, J) arrived after warmup, not completed
     trace: Optional[torch.Tensor] = None   # (B, T, 3) arrivals, departures,
     #                                        tasks in network per slot
+    stats: Optional[SimStats] = None       # with simulate(stats=True)
 
 
 class EpisodeEngine:
@@ -1081,13 +1176,19 @@ class EpisodeEngine:
 
     def simulate(self, jobs: JobBatch, result: EpisodeResult,
                  arrivals: torch.Tensor, warmup: int = 0,
-                 trace: bool = False) -> SimResult:
+                 trace: bool = False, stats: bool = False,
+                 late_after=None) -> SimResult:
         """Replay an episode's decisions packet by packet: the per-timeslot
         simulator of ``sim.timeslot`` over ``result``'s routes, all B graphs
         in one HIP launch on the GPU.  ``arrivals`` is (B, T, J) counts
         (``draw_arrivals``).  On the CPU engine each case runs
         ``simulate_routes`` on its own fp64 arrays, so B=1 equals
-        ``sim.timeslot.simulate``."""
+        ``sim.timeslot.simulate``.  ``stats=True`` also fills
+        ``SimResult.stats`` (``SimStats``): delay maxima, tails and
+        histograms, the age of the backlog and per-resource queue
+        statistics; ``late_after`` (an int or a (B,) tensor) is the sojourn
+        above which a task counts as late, by default ``floor(T)`` of each
+        graph, the analytic congestion horizon."""
         if result.dst is None or result.route_links is None \
                 or result.nhop is None:
             raise ValueError("simulate: the EpisodeResult carries no routes")
@@ -1097,15 +1198,25 @@ class EpisodeEngine:
             (tuple(arrivals.shape), (B, J))
         T_sim = arrivals.shape[1]
         warmup = int(warmup)
+        st = None
+        if stats:
+            if late_after is None:
+                late_after = torch.floor(self.T_arr)
+            if not torch.is_tensor(late_after):
+                late_after = torch.full((B,), int(late_after))
+            late_after = late_after.to(device=self.device,
+                                       dtype=torch.int32).reshape(B)
         if self.use_hip:
-            delay_sum, count, tr = ops.timeslot_sim(
+            out = ops.timeslot_sim(
                 arrivals, result.route_links, result.nhop, result.dst,
                 jobs.mask, jobs.ul, jobs.dl, self.link_rates, self.proc_bws,
                 self.k_conf_indptr, self.k_conf_base, self.k_conf_cols,
                 self.k_E_arr, self.k_N_arr, self.T_arr, warmup=warmup,
-                trace=trace)
+                trace=trace, stats=stats, late_after=late_after)
+            delay_sum, count, tr = out[:3]
+            st = out[3] if stats else None
         else:
-            from .sim.timeslot import simulate_routes
+            from .sim.timeslot import num_delay_bins, simulate_routes
             if arrivals.numel() and (int(arrivals.max()) > 255
                                      or int(arrivals.min()) < 0):
                 raise ValueError("simulate: arrival counts must lie in "
@@ -1115,6 +1226,9 @@ class EpisodeEngine:
             tr = torch.zeros(B, T_sim, 3, dtype=torch.int32) if trace \
                 else None
             arr_np = arrivals.cpu().numpy()
+            if stats:
+                st = ops.empty_stats(B, J, self.E + self.N,
+                                     num_delay_bins(T_sim))
             for b, g in enumerate(self.cases):
                 k = int(jobs.mask[b].sum())
                 assert bool(jobs.mask[b, :k].all()), "mask is a prefix"
@@ -1124,7 +1238,11 @@ class EpisodeEngine:
                     result.dst[b, :k].cpu().numpy(),
                     result.route_links[b, :k].cpu().numpy(),
                     result.nhop[b, :k].cpu().numpy(), arr_np[b][:, :k],
-                    warmup=warmup, trace=trace)
+                    warmup=warmup, trace=trace, stats=stats,
+                    late_after=int(late_after[b]) if stats else None)
+                if stats:
+                    ops.fill_stats(st, b, out[-1], slice(0, k),
+                                   g.num_links, self.E)
                 delay_sum[b, :k] = torch.as_tensor(out[0])
                 count[b, :k] = torch.as_tensor(out[1]).to(torch.int32)
                 if trace:
@@ -1135,6 +1253,8 @@ class EpisodeEngine:
             delay_sum = delay_sum.to(self.device)
             count = count.to(self.device)
             tr = tr.to(self.device) if trace else None
+            if stats:
+                st = {k: v.to(self.device) for k, v in st.items()}
         cnt = count.to(torch.float64)
         mean = torch.where(count > 0,
                            delay_sum.to(torch.float64) / cnt.clamp(min=1),
@@ -1142,8 +1262,13 @@ class EpisodeEngine:
         arrived = torch.where(jobs.mask[:, None, :], arrivals,
                               torch.zeros_like(arrivals))[:, warmup:] \
             .sum(1, dtype=torch.int64)
+        if stats:
+            st = SimStats(**st, delay_sum=delay_sum, count=count,
+                          late_after=late_after, num_links=self.E,
+                          T_sim=int(T_sim), warmup=warmup)
         return SimResult(delay_sum=delay_sum, count=count, mean_delay=mean,
-                         backlog=arrived - count.to(torch.int64), trace=tr)
+                         backlog=arrived - count.to(torch.int64), trace=tr,
+                         stats=st)
 
     def _collect_per_sample_grads(self):
         """Slice the per-graph dW/db partials stashed by ChebStackFn's

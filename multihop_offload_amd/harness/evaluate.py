@@ -17,7 +17,7 @@ import os
 
 import torch
 
-from ..engine import EpisodeEngine
+from ..engine import EpisodeEngine, hist_percentile
 from ..models.chebconv import ChebConvStack
 from ..utils.checkpoint import latest_checkpoint, load, model_dir
 from .train_batched import build_training_cases
@@ -25,7 +25,8 @@ from .train_batched import build_training_cases
 
 def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
              device, dtype, workers: int = 8, lam_margin: float = 0.0,
-             refine: int = 0, simulate: int = 0, sim_warmup: int = 0):
+             refine: int = 0, simulate: int = 0, sim_warmup: int = 0,
+             sim_stats: bool = False):
     """Returns per-method aggregate {tau, congest_jobs, num_jobs} summed /
     averaged over all (size, case, instance).  ``simulate`` > 0 also replays
     every episode's routes in the per-timeslot packet simulator for that
@@ -34,11 +35,23 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
     adds ``sim_tau`` (task-weighted mean simulated sojourn of the tasks
     that arrived after ``sim_warmup`` and completed), ``sim_backlog_ratio``
     (the share of those arrivals still in the network at the end) and
-    ``sim_tasks`` (completed tasks)."""
+    ``sim_tasks`` (completed tasks).  ``sim_stats`` runs the simulator in
+    its statistics mode and adds, over the same tasks: ``sim_p50`` /
+    ``sim_p95`` / ``sim_p99`` (histogram upper bounds on the sojourn
+    percentiles, all histograms merged), ``sim_late_ratio`` (share of the
+    completed tasks later than the graph's horizon T, the packet-level
+    counterpart of ``congest_ratio``), ``sim_tau_censored`` (mean sojourn
+    with every task still in the network counted at its age so far: a lower
+    bound that does not drop them) and ``sim_link_util_max`` /
+    ``sim_node_util_max`` (the busiest link's and node's share of busy
+    slots)."""
     def fresh():
         return {"tau_sum": 0.0, "tau_n": 0, "congest": 0, "jobs": 0,
                 "ratio_sum": 0.0, "ratio_n": 0, "sim_delay": 0,
-                "sim_tasks": 0, "sim_backlog": 0, "sim_arrived": 0}
+                "sim_tasks": 0, "sim_backlog": 0, "sim_arrived": 0,
+                "sim_hist": None, "sim_dmax": 0, "sim_late": 0,
+                "sim_stuck_age": 0, "sim_link_util": 0.0,
+                "sim_node_util": 0.0}
 
     def fields(d, jobs_too=False):
         out = {"tau": d["tau_sum"] / max(d["tau_n"], 1),
@@ -52,6 +65,19 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
             out["sim_backlog_ratio"] = (d["sim_backlog"]
                                         / max(d["sim_arrived"], 1))
             out["sim_tasks"] = d["sim_tasks"]
+        if simulate and sim_stats:
+            for name, q in (("sim_p50", 0.5), ("sim_p95", 0.95),
+                            ("sim_p99", 0.99)):
+                out[name] = float(hist_percentile(
+                    d["sim_hist"], torch.tensor(d["sim_dmax"]), q))
+            out["sim_late_ratio"] = (d["sim_late"] / d["sim_tasks"]
+                                     if d["sim_tasks"] else float("nan"))
+            seen = d["sim_tasks"] + d["sim_backlog"]
+            out["sim_tau_censored"] = (
+                (d["sim_delay"] + d["sim_stuck_age"]) / seen
+                if seen else float("nan"))
+            out["sim_link_util_max"] = d["sim_link_util"]
+            out["sim_node_util_max"] = d["sim_node_util"]
         return out
 
     agg = {m: fresh() for m in ("baseline", "local", "GNN")}
@@ -82,7 +108,7 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
                 r = res.delay_emp / bl
                 ok = torch.isfinite(r)
                 sim = (engine.simulate(jobs, res, arrivals,
-                                       warmup=sim_warmup)
+                                       warmup=sim_warmup, stats=sim_stats)
                        if simulate else None)
                 for d in (agg[m], ps[m]):
                     d["tau_sum"] += float(torch.nansum(res.tau))
@@ -97,6 +123,23 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
                         d["sim_backlog"] += int(sim.backlog.sum())
                         d["sim_arrived"] += int(sim.backlog.sum()
                                                 + sim.count.sum())
+                    if sim is not None and sim.stats is not None:
+                        st = sim.stats
+                        hist = st.delay_hist.sum((0, 1),
+                                                 dtype=torch.int64).cpu()
+                        d["sim_hist"] = hist if d["sim_hist"] is None \
+                            else d["sim_hist"] + hist
+                        d["sim_dmax"] = max(d["sim_dmax"],
+                                            int(st.delay_max.max()))
+                        d["sim_late"] += int(st.late.sum())
+                        d["sim_stuck_age"] += int(st.stuck_age.sum())
+                        util = st.utilization()
+                        E = st.num_links
+                        d["sim_link_util"] = max(
+                            d["sim_link_util"],
+                            float(util[:, :E].max()) if E else 0.0)
+                        d["sim_node_util"] = max(d["sim_node_util"],
+                                                 float(util[:, E:].max()))
         engine.check_overflow()       # strict: truncated walks void an eval
         per_size[n] = {m: fields(d) for m, d in ps.items()}
     summary = {m: fields(d, jobs_too=True) for m, d in agg.items()}
@@ -132,8 +175,14 @@ def main(argv=None):
                          "the analytic fields (0 = off)")
     ap.add_argument("--sim-warmup", type=int, default=0,
                     help="slots whose arrivals the simulated figures skip")
+    ap.add_argument("--sim-stats", action="store_true",
+                    help="with --simulate: also report sim_p50 / sim_p95 / "
+                         "sim_p99, sim_late_ratio, sim_tau_censored, "
+                         "sim_link_util_max and sim_node_util_max")
     ap.add_argument("--out", type=str, default="out/eval_summary.json")
     args = ap.parse_args(argv)
+    if args.sim_stats and not args.simulate:
+        ap.error("--sim-stats requires --simulate T_SIM")
 
     device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
     dtype = torch.float32 if device.startswith("cuda") else torch.float64
@@ -152,7 +201,8 @@ def main(argv=None):
                                  lam_margin=args.lam_margin,
                                  refine=args.refine,
                                  simulate=args.simulate,
-                                 sim_warmup=args.sim_warmup)
+                                 sim_warmup=args.sim_warmup,
+                                 sim_stats=args.sim_stats)
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     with open(args.out, "w") as f:
         json.dump({"summary": summary, "per_size": per_size,

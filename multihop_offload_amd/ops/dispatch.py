@@ -76,6 +76,38 @@ def queue_csr_force_global(on: bool) -> None:
     _require_hip().queue_csr_force_global(bool(on))
 
 
+# the statistics of timeslot_sim(stats=True), in the extension's order
+STAT_KEYS = ("delay_max", "late", "delay_hist", "stuck", "stuck_age",
+             "qlen_sum", "qlen_max", "busy_slots", "nb_sum")
+_STAT_I64 = ("stuck_age", "qlen_sum", "nb_sum")
+_STAT_PER_JOB = STAT_KEYS[:5]
+
+
+def empty_stats(B: int, J: int, R: int, NB: int) -> dict:
+    """Zeroed CPU statistics tensors of a (B, J) batch with R = E + N
+    resource columns and NB histogram bins, in the kernel's dtypes."""
+    out = {}
+    for k in STAT_KEYS:
+        shape = (B, J, NB) if k == "delay_hist" else \
+            (B, J) if k in _STAT_PER_JOB else (B, R)
+        out[k] = torch.zeros(shape, dtype=torch.int64 if k in _STAT_I64
+                             else torch.int32)
+    return out
+
+
+def fill_stats(st: dict, b: int, one: dict, idx, Eb: int, E: int) -> None:
+    """Place one ``simulate_routes(stats=True)`` dict into row b: its jobs
+    at the job slots ``idx``, its Eb links at columns [0, Eb) and its nodes
+    from column E on."""
+    for k in STAT_KEYS:
+        v = torch.as_tensor(one[k])
+        if k in _STAT_PER_JOB:
+            st[k][b, idx] = v
+        else:
+            st[k][b, :Eb] = v[:Eb]
+            st[k][b, E:E + len(v) - Eb] = v[Eb:]
+
+
 def timeslot_lds_plan(N: int, E: int, J: int) -> dict:
     """LDS plan of the timeslot simulator kernel for a batch of N nodes, at
     most E links and J job slots: ``lds_bytes``, ``threads``, ``large``,
@@ -83,9 +115,18 @@ def timeslot_lds_plan(N: int, E: int, J: int) -> dict:
     return dict(_require_hip().timeslot_lds_plan(int(N), int(E), int(J)))
 
 
+def timeslot_stats_lds_plan(N: int, E: int, J: int) -> dict:
+    """LDS plan of the simulator's statistics launch
+    (``timeslot_sim(stats=True)``): the base plan's regions, then the live
+    queue lengths and the per-resource accumulators."""
+    return dict(_require_hip().timeslot_stats_lds_plan(int(N), int(E),
+                                                       int(J)))
+
+
 def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
                  proc_bws, conf_indptr, conf_base, conf_cols, E_arr, n_arr,
-                 T_arr=None, warmup: int = 0, trace: bool = False):
+                 T_arr=None, warmup: int = 0, trace: bool = False,
+                 stats: bool = False, late_after=None):
     """Batched per-timeslot packet simulation of ``sim.timeslot``.
 
     ``arrivals`` (B,T,J) integer counts (at most 255 each; masked job slots
@@ -95,7 +136,15 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
     int32 (B,J), trace int32 (B,T,3) or None)`` with the trace columns
     (arrivals, departures, tasks in network).  GPU tensors run the HIP
     kernel (required — no eager fallback); CPU tensors loop over
-    ``simulate_routes``."""
+    ``simulate_routes``.
+
+    ``stats=True`` returns a 4-tuple whose last element is a dict of the
+    integer statistics of ``sim.timeslot.simulate_routes(stats=True)``
+    (``STAT_KEYS``): the per-job ones (B,J) (``delay_hist`` (B,J,NB)), the
+    per-resource ones (B,E+N) with link l at column l and node v at column
+    E + v, E the batch-maximum link count; masked job slots and padded
+    links and nodes are zero.  ``late_after`` is an int32 (B,) tensor or an
+    int (default ``T``: no sojourn is late)."""
     B, T, J = arrivals.shape
     if arrivals.numel() and (int(arrivals.max()) > 255
                              or int(arrivals.min()) < 0):
@@ -109,6 +158,14 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
     if warmup < 0:
         raise ValueError("timeslot_sim: warmup must be non-negative")
 
+    if stats:
+        if late_after is None:
+            late_after = T
+        if not torch.is_tensor(late_after):
+            late_after = torch.full((B,), int(late_after), dtype=torch.int32)
+        late_after = late_after.to(device=arr.device, dtype=torch.int32) \
+            .reshape(B).contiguous()
+
     if arr.is_cuda:
         ext = _require_hip()
         slot_off = torch.zeros(B, T + 1, dtype=torch.int32, device=arr.device)
@@ -116,7 +173,7 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
         pool = int(slot_off[:, -1].max()) if B else 0
         if T_arr is None:
             T_arr = torch.zeros(B, dtype=torch.float32, device=arr.device)
-        delay_sum, count, error, tr = ext.timeslot_sim(
+        args = (
             arr, slot_off, route_links.to(torch.int32).contiguous(),
             nhop.to(torch.int32).contiguous(),
             dst.to(torch.int64).contiguous(), mask.contiguous(),
@@ -126,25 +183,37 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
             proc_bws.to(torch.float32).contiguous(),
             T_arr.to(torch.float32).contiguous(), E_arr, n_arr, warmup,
             pool, bool(trace))
+        if stats:
+            from ..sim.timeslot import num_delay_bins
+            out = ext.timeslot_sim_stats(*args, late_after,
+                                         num_delay_bins(T))
+        else:
+            out = ext.timeslot_sim(*args)
+        delay_sum, count, error, tr = out[:4]
         if bool(error.any()):
             bad = torch.nonzero(error).flatten().tolist()
             raise RuntimeError(
                 "timeslot_sim: guard rail tripped (input out of range, pool "
                 f"or loop bound) in graphs {bad[:8]}, bits "
                 f"{error[bad[:8]].tolist()}")
+        if stats:
+            return delay_sum, count, (tr if trace else None), \
+                dict(zip(STAT_KEYS, out[4:]))
         return delay_sum, count, (tr if trace else None)
 
     from types import SimpleNamespace
 
     import numpy as np
 
-    from ..sim.timeslot import simulate_routes
+    from ..sim.timeslot import num_delay_bins, simulate_routes
     delay_sum = torch.zeros(B, J, dtype=torch.int64)
     count = torch.zeros(B, J, dtype=torch.int32)
     tr = torch.zeros(B, T, 3, dtype=torch.int32) if trace else None
     cip = conf_indptr.numpy()
     cols = conf_cols.numpy()
     N = proc_bws.shape[1]
+    E = link_rates.shape[1]
+    st = empty_stats(B, J, E + N, num_delay_bins(T)) if stats else None
     for b in range(B):
         Eb = int(E_arr[b])
         lo = int(conf_base[b])
@@ -158,11 +227,16 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
             g, ul[b, idx].numpy().astype(np.float64),
             dl[b, idx].numpy().astype(np.float64), dst[b, idx].numpy(),
             route_links[b, idx].numpy(), nhop[b, idx].numpy(),
-            arr[b][:, idx].numpy(), warmup=warmup, trace=trace)
+            arr[b][:, idx].numpy(), warmup=warmup, trace=trace,
+            stats=stats, late_after=int(late_after[b]) if stats else None)
+        if stats:
+            fill_stats(st, b, out[-1], idx, Eb, E)
         delay_sum[b, idx] = torch.as_tensor(out[0])
         count[b, idx] = torch.as_tensor(out[1]).to(torch.int32)
         if trace:
             for k, name in enumerate(("arrivals", "departures",
                                       "pkts_in_network")):
                 tr[b, :, k] = torch.as_tensor(out[2][name]).to(torch.int32)
+    if stats:
+        return delay_sum, count, tr, st
     return delay_sum, count, tr

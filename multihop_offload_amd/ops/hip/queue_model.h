@@ -504,24 +504,50 @@ struct TimeslotPlan : Launch {
     int head, tail, fhead, ftgt0, fcnt, jfirst, fmask, busy, arr, jres,
         jnext, jnh, jdst, misc;
 };
+inline void timeslot_regions(TimeslotPlan& p, Carve& c, int N, int E,
+                             int J) {
+    const size_t R = (size_t)E + N;
+    p.head = c.lds(R);
+    p.tail = c.lds(R);
+    p.fhead = c.lds(R);
+    p.ftgt0 = c.lds(R);
+    p.fcnt = c.lds(R);
+    p.jfirst = c.lds(R);
+    p.fmask = c.lds((R + 31) / 32);
+    p.busy = c.lds(E);
+    p.arr = c.lds(J);
+    p.jres = c.lds(J);
+    p.jnext = c.lds(J);
+    p.jnh = c.lds(J);
+    p.jdst = c.lds(J);
+    p.misc = c.lds(4);
+}
 inline TimeslotPlan timeslot_plan(int N, int E, int J) {
     return make_plan<TimeslotPlan>(
         launch_threads(E, N), [=](TimeslotPlan& p, Carve& c) {
+            timeslot_regions(p, c, N, E, J);
+        });
+}
+
+// The statistics launch of timeslot_sim: the base regions in the same order,
+// then the live queue length, the sampled maximum and the busy-slot count
+// (one word per resource), one pad word where the count so far is odd, and
+// the two 64-bit sums (queue length per resource, nb per link).  With W the
+// base plan's words: 4 * (W + 3 R + (W + 3 R) % 2 + 2 R + 2 E) bytes.
+struct TimeslotStatsPlan : TimeslotPlan {
+    int qlen, qmax, bslots, qsum, nbsum;
+};
+inline TimeslotStatsPlan timeslot_stats_plan(int N, int E, int J) {
+    return make_plan<TimeslotStatsPlan>(
+        launch_threads(E, N), [=](TimeslotStatsPlan& p, Carve& c) {
             const size_t R = (size_t)E + N;
-            p.head = c.lds(R);
-            p.tail = c.lds(R);
-            p.fhead = c.lds(R);
-            p.ftgt0 = c.lds(R);
-            p.fcnt = c.lds(R);
-            p.jfirst = c.lds(R);
-            p.fmask = c.lds((R + 31) / 32);
-            p.busy = c.lds(E);
-            p.arr = c.lds(J);
-            p.jres = c.lds(J);
-            p.jnext = c.lds(J);
-            p.jnh = c.lds(J);
-            p.jdst = c.lds(J);
-            p.misc = c.lds(4);
+            timeslot_regions(p, c, N, E, J);
+            p.qlen = c.lds(R);
+            p.qmax = c.lds(R);
+            p.bslots = c.lds(R);
+            c.lds(c.floats & 1);            // the 64-bit rows start even
+            p.qsum = c.lds(2 * R);
+            p.nbsum = c.lds(2 * (size_t)E);
         });
 }
 

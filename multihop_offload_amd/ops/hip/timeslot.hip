@@ -11,6 +11,12 @@
 // so delay_sum / count / trace equal simulate_routes integer for integer on
 // the fp32-rounded inputs.
 //
+// Statistics mode (timeslot_sim_stats) is the same kernel text instantiated
+// with Stats = true: its own LDS plan (qm::timeslot_stats_plan) adds the live
+// queue lengths and the per-resource accumulators, the per-job delay figures
+// go to global memory beside delay_sum / count, and two more phases run after
+// the last slot.  Stats = false compiles to the statistics-free kernel.
+//
 // A graph whose guard rails trip (tsim::ERR) stops stepping; error[b] carries
 // the bits and the Python wrapper raises.
 
@@ -21,6 +27,26 @@
 
 namespace {
 
+struct StatArgs {                   // the statistics outputs, all prezeroed
+    const int* late_after;          // (B)
+    int* delay_max;                 // (B,J)
+    int* late;                      // (B,J)
+    int* delay_hist;                // (B,J,nbins)
+    int* stuck;                     // (B,J)
+    long long* stuck_age;           // (B,J)
+    long long* qlen_sum;            // (B,E+N), as the three below
+    int* qlen_max;
+    int* busy_slots;
+    long long* nb_sum;
+    int nbins;
+};
+template <bool Stats>
+using plan_t = std::conditional_t<Stats, qm::TimeslotStatsPlan,
+                                  qm::TimeslotPlan>;
+
+// StatArg is the one StatArgs of the statistics launch and nothing at all
+// otherwise, so that Stats = false keeps the plain kernel's argument list.
+template <bool Stats, class... StatArg>
 __global__ void timeslot_kernel(
     const unsigned char* __restrict__ arrivals,   // (B,T,J)
     const int* __restrict__ slot_off,             // (B,T+1)
@@ -38,8 +64,8 @@ __global__ void timeslot_kernel(
     int* __restrict__ count,                      // (B,J) out
     int* __restrict__ error,                      // (B) out
     int* __restrict__ trace,                      // (B,T,3) prezeroed, or null
-    const qm::TimeslotPlan p, int N, int J, int H, int T, int warmup,
-    int P) {
+    const plan_t<Stats> p, int N, int J, int H, int T, int warmup, int P,
+    const StatArg... stat_arg) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     int* w = reinterpret_cast<int*>(smem_raw);
 
@@ -78,6 +104,26 @@ __global__ void timeslot_kernel(
     st.delay_sum = delay_sum + (size_t)b * J;
     st.count = count + (size_t)b * J;
     st.trace = trace ? trace + (size_t)b * T * 3 : nullptr;
+    if constexpr (Stats) {
+        const StatArgs& sa = (stat_arg, ...);
+        const size_t RS = (size_t)tb.E + N;     // per-resource output stride
+        c.late_after = sa.late_after[b];
+        c.nbins = sa.nbins;
+        c.node_col = tb.E;
+        st.qlen = w + p.qlen;   st.qmax = w + p.qmax;
+        st.bslots = w + p.bslots;
+        st.qsum = reinterpret_cast<long long*>(w + p.qsum);
+        st.nbsum = reinterpret_cast<long long*>(w + p.nbsum);
+        st.delay_max = sa.delay_max + (size_t)b * J;
+        st.late = sa.late + (size_t)b * J;
+        st.delay_hist = sa.delay_hist + (size_t)b * J * sa.nbins;
+        st.stuck = sa.stuck + (size_t)b * J;
+        st.stuck_age = sa.stuck_age + (size_t)b * J;
+        st.qlen_sum = sa.qlen_sum + b * RS;
+        st.qlen_max = sa.qlen_max + b * RS;
+        st.busy_slots = sa.busy_slots + b * RS;
+        st.nb_sum = sa.nb_sum + b * RS;
+    }
 
     // the ragged link count must fit the carve before anything indexes by it
     const bool sized = c.Eb >= 0 && c.Eb <= tb.E;
@@ -91,31 +137,40 @@ __global__ void timeslot_kernel(
     }
     tsim::init_jobs(c, st, tid, nt);
     __syncthreads();
-    tsim::init_queues(c, st, tid, nt);
+    tsim::init_queues<Stats>(c, st, tid, nt);
     // The error word is only ever read through the barrier itself: a thread
     // that sets it reads its own store on arrival, so every thread gets the
     // same answer and the workgroup leaves the loop together.
     int err = __syncthreads_or(st.misc[tsim::ERR]);
     for (int t = 0; t < T && !err; ++t) {
-        tsim::arrive(c, st, t, tid, nt);
+        tsim::arrive<Stats>(c, st, t, tid, nt);
         __syncthreads();
-        tsim::serve(c, st, t, tid, nt);
+        tsim::serve<Stats>(c, st, t, tid, nt);
         __syncthreads();
-        tsim::handover(c, st, t, tid, nt);
+        tsim::handover<Stats>(c, st, t, tid, nt);
         err = __syncthreads_or(st.misc[tsim::ERR]);
+    }
+    if constexpr (Stats) {
+        if (!err) {
+            tsim::tally_backlog(c, st, tid, nt);
+            tsim::store_resource_stats(c, st, tid, nt);
+            __syncthreads();
+        }
     }
     if (tid == 0) error[b] = st.misc[tsim::ERR];
 }
 
-}  // namespace
-
-std::vector<torch::Tensor> timeslot_sim_hip(
+// Both entry points: checks, allocations and the launch of one instantiation.
+// Stats appends the nine statistic tensors to the four of the plain launch.
+template <bool Stats>
+std::vector<torch::Tensor> timeslot_launch(
     torch::Tensor arrivals, torch::Tensor slot_off, torch::Tensor route_links,
     torch::Tensor nhop, torch::Tensor dst, torch::Tensor mask,
     torch::Tensor ul, torch::Tensor dl, torch::Tensor conf_indptr,
     torch::Tensor conf_base, torch::Tensor conf_cols, torch::Tensor rates,
     torch::Tensor bw, torch::Tensor T_arr, torch::Tensor E_arr,
-    torch::Tensor n_arr, long warmup, long pool, bool want_trace) {
+    torch::Tensor n_arr, long warmup, long pool, bool want_trace,
+    torch::Tensor late_after, long nbins) {
     const int B = arrivals.size(0), T = arrivals.size(1);
     const int J = arrivals.size(2);
     const int N = bw.size(1), E = rates.size(1), H = route_links.size(2);
@@ -145,8 +200,19 @@ std::vector<torch::Tensor> timeslot_sim_hip(
                 E_arr.numel() == B && n_arr.numel() == B &&
                 conf_base.numel() >= B, "batch tables disagree on B or E");
     TORCH_CHECK(pool >= 0 && warmup >= 0, "pool, warmup: non-negative");
-    const qm::TimeslotPlan p = qm::timeslot_plan(N, E, J);
-    TORCH_CHECK(p.fits, "graph too large for LDS timeslot_sim");
+    plan_t<Stats> p;
+    if constexpr (Stats) {
+        TORCH_CHECK(late_after.is_cuda() && late_after.is_contiguous() &&
+                    late_after.scalar_type() == torch::kInt32 &&
+                    late_after.numel() == B, "late_after: int32 (B)");
+        TORCH_CHECK(nbins >= 1 && nbins <= T + 1,
+                    "nbins: sim.timeslot.num_delay_bins(T)");
+        p = qm::timeslot_stats_plan(N, E, J);
+        TORCH_CHECK(p.fits, "graph too large for LDS timeslot_sim_stats");
+    } else {
+        p = qm::timeslot_plan(N, E, J);
+        TORCH_CHECK(p.fits, "graph too large for LDS timeslot_sim");
+    }
 
     auto opts_i = nhop.options();
     const long P = pool > 0 ? pool : 1;
@@ -157,28 +223,104 @@ std::vector<torch::Tensor> timeslot_sim_hip(
     auto error = torch::zeros({B}, opts_i);
     torch::Tensor trace;
     if (want_trace) trace = torch::zeros({B, T, 3}, opts_i);
+    StatArgs sa{};
+    std::vector<torch::Tensor> stat_out;
+    if constexpr (Stats) {
+        auto opts_l = opts_i.dtype(torch::kInt64);
+        auto delay_max = torch::zeros({B, J}, opts_i);
+        auto late = torch::zeros({B, J}, opts_i);
+        auto delay_hist = torch::zeros({B, J, nbins}, opts_i);
+        auto stuck = torch::zeros({B, J}, opts_i);
+        auto stuck_age = torch::zeros({B, J}, opts_l);
+        auto qlen_sum = torch::zeros({B, E + N}, opts_l);
+        auto qlen_max = torch::zeros({B, E + N}, opts_i);
+        auto busy_slots = torch::zeros({B, E + N}, opts_i);
+        auto nb_sum = torch::zeros({B, E + N}, opts_l);
+        sa.late_after = late_after.data_ptr<int>();
+        sa.delay_max = delay_max.data_ptr<int>();
+        sa.late = late.data_ptr<int>();
+        sa.delay_hist = delay_hist.data_ptr<int>();
+        sa.stuck = stuck.data_ptr<int>();
+        sa.stuck_age =
+            reinterpret_cast<long long*>(stuck_age.data_ptr<long>());
+        sa.qlen_sum = reinterpret_cast<long long*>(qlen_sum.data_ptr<long>());
+        sa.qlen_max = qlen_max.data_ptr<int>();
+        sa.busy_slots = busy_slots.data_ptr<int>();
+        sa.nb_sum = reinterpret_cast<long long*>(nb_sum.data_ptr<long>());
+        sa.nbins = (int)nbins;
+        stat_out = {delay_max, late, delay_hist, stuck, stuck_age,
+                    qlen_sum, qlen_max, busy_slots, nb_sum};
+    }
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(
-        timeslot_kernel, dim3(B), dim3(p.threads), p.lds_bytes,
-        stream.stream(), arrivals.data_ptr<uint8_t>(),
-        slot_off.data_ptr<int>(), route_links.data_ptr<int>(),
-        nhop.data_ptr<int>(), dst.data_ptr<long>(), mask.data_ptr<bool>(),
-        ul.data_ptr<float>(), dl.data_ptr<float>(),
-        qm::tables(conf_indptr, conf_base, conf_cols, rates, bw, T_arr,
-                   E_arr),
-        n_arr.data_ptr<int>(), pool_i.data_ptr<int>(),
-        pool_rem.data_ptr<double>(),
-        reinterpret_cast<long long*>(delay_sum.data_ptr<long>()),
-        count.data_ptr<int>(), error.data_ptr<int>(),
-        want_trace ? trace.data_ptr<int>() : nullptr, p, N, J, H, T,
-        (int)warmup, (int)P);
+    auto launch = [&](auto kernel, auto... stat_arg) {
+        hipLaunchKernelGGL(
+            kernel, dim3(B), dim3(p.threads), p.lds_bytes, stream.stream(),
+            arrivals.data_ptr<uint8_t>(), slot_off.data_ptr<int>(),
+            route_links.data_ptr<int>(), nhop.data_ptr<int>(),
+            dst.data_ptr<long>(), mask.data_ptr<bool>(),
+            ul.data_ptr<float>(), dl.data_ptr<float>(),
+            qm::tables(conf_indptr, conf_base, conf_cols, rates, bw, T_arr,
+                       E_arr),
+            n_arr.data_ptr<int>(), pool_i.data_ptr<int>(),
+            pool_rem.data_ptr<double>(),
+            reinterpret_cast<long long*>(delay_sum.data_ptr<long>()),
+            count.data_ptr<int>(), error.data_ptr<int>(),
+            want_trace ? trace.data_ptr<int>() : nullptr, p, N, J, H, T,
+            (int)warmup, (int)P, stat_arg...);
+    };
+    if constexpr (Stats) launch(timeslot_kernel<true, StatArgs>, sa);
+    else launch(timeslot_kernel<false>);
     if (!want_trace) trace = torch::empty({0}, opts_i);
-    return {delay_sum, count, error, trace};
+    std::vector<torch::Tensor> out = {delay_sum, count, error, trace};
+    out.insert(out.end(), stat_out.begin(), stat_out.end());
+    return out;
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> timeslot_sim_hip(
+    torch::Tensor arrivals, torch::Tensor slot_off, torch::Tensor route_links,
+    torch::Tensor nhop, torch::Tensor dst, torch::Tensor mask,
+    torch::Tensor ul, torch::Tensor dl, torch::Tensor conf_indptr,
+    torch::Tensor conf_base, torch::Tensor conf_cols, torch::Tensor rates,
+    torch::Tensor bw, torch::Tensor T_arr, torch::Tensor E_arr,
+    torch::Tensor n_arr, long warmup, long pool, bool want_trace) {
+    return timeslot_launch<false>(
+        arrivals, slot_off, route_links, nhop, dst, mask, ul, dl, conf_indptr,
+        conf_base, conf_cols, rates, bw, T_arr, E_arr, n_arr, warmup, pool,
+        want_trace, torch::Tensor(), 0);
+}
+
+// timeslot_sim plus the statistics of sim/timeslot.py (stats=True): returns
+// delay_sum, count, error, trace, then delay_max, late, delay_hist, stuck,
+// stuck_age (per job) and qlen_sum, qlen_max, busy_slots, nb_sum (B, E+N).
+// `nbins` is sim.timeslot.num_delay_bins(T); a sojourn whose bin is not below
+// it trips the pool guard rail instead of being stored.
+std::vector<torch::Tensor> timeslot_sim_stats_hip(
+    torch::Tensor arrivals, torch::Tensor slot_off, torch::Tensor route_links,
+    torch::Tensor nhop, torch::Tensor dst, torch::Tensor mask,
+    torch::Tensor ul, torch::Tensor dl, torch::Tensor conf_indptr,
+    torch::Tensor conf_base, torch::Tensor conf_cols, torch::Tensor rates,
+    torch::Tensor bw, torch::Tensor T_arr, torch::Tensor E_arr,
+    torch::Tensor n_arr, long warmup, long pool, bool want_trace,
+    torch::Tensor late_after, long nbins) {
+    return timeslot_launch<true>(
+        arrivals, slot_off, route_links, nhop, dst, mask, ul, dl, conf_indptr,
+        conf_base, conf_cols, rates, bw, T_arr, E_arr, n_arr, warmup, pool,
+        want_trace, late_after, nbins);
 }
 
 py::dict timeslot_lds_plan(long N, long E, long J) {
     using namespace pybind11::literals;
     const qm::TimeslotPlan p = qm::timeslot_plan((int)N, (int)E, (int)J);
+    return py::dict("lds_bytes"_a = p.lds_bytes, "large"_a = p.large,
+                    "threads"_a = p.threads, "fits"_a = p.fits);
+}
+
+py::dict timeslot_stats_lds_plan(long N, long E, long J) {
+    using namespace pybind11::literals;
+    const qm::TimeslotStatsPlan p =
+        qm::timeslot_stats_plan((int)N, (int)E, (int)J);
     return py::dict("lds_bytes"_a = p.lds_bytes, "large"_a = p.large,
                     "threads"_a = p.threads, "fits"_a = p.fits);
 }

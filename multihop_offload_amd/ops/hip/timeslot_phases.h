@@ -20,6 +20,14 @@
 //                 tasks whose next leg is r; thread 0 writes the
 //                 trace row; slot t+1's arrival counts are staged
 //
+// Statistics mode: every phase is a template on `Stats`, false by default, so
+// the plain names are the statistics-free simulator, unchanged.  With Stats
+// the owner of r also keeps qlen[r], samples it after the arrivals of every
+// slot t >= warmup (qsum / qmax / bslots, and nbsum in serve), the owner of a
+// job's last leg adds the sojourn to the job's max / late / histogram, and
+// two phases follow the last slot: tally_backlog and store_resource_stats.
+// All of it is integers, each word with one writer or an integer sum.
+//
 // Guard rails: every index read from memory is range-checked before use and
 // every loop has a bound derived from the pool capacity P; a violation sets
 // st.misc[ERR] and the caller stops stepping that graph.
@@ -34,9 +42,12 @@
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define TSIM_COUNT_ADD(p, v) atomicAdd((p), (v))   // integer count only
+#define TSIM_COUNT_ADD64(p, v) \
+    atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)(v))
 #define TSIM_SET_BITS(p, v) atomicOr((p), (v))     // a set: no order in it
 #else
 #define TSIM_COUNT_ADD(p, v) (*(p) += (v))
+#define TSIM_COUNT_ADD64(p, v) (*(p) += (v))
 #define TSIM_SET_BITS(p, v) (*(p) |= (v))
 #endif
 
@@ -64,6 +75,10 @@ struct Case {                       // one graph, read-only
     const bool* mask;               // (J)
     const float* ul;                // (J)
     const float* dl;                // (J)
+    // statistics mode only
+    int late_after = 0;             // sojourns above it count as late
+    int nbins = 0;                  // delay_bin(T) + 1 histogram bins
+    int node_col = 0;               // output column of node 0 (batch max E)
 };
 
 struct State {                      // one graph, mutable
@@ -94,10 +109,36 @@ struct State {                      // one graph, mutable
     long long* delay_sum;           // (J)
     int* count;                     // (J)
     int* trace;                     // (T,3) or null
+    // statistics mode only: live length and accumulators (LDS on the GPU),
+    // indexed by resource id
+    int* qlen = nullptr;            // (R) tasks in r's FIFO
+    long long* qsum = nullptr;      // (R) sum of qlen over the sampled slots
+    int* qmax = nullptr;            // (R) largest sampled qlen
+    int* bslots = nullptr;          // (R) sampled slots with qlen > 0
+    long long* nbsum = nullptr;     // (Eb) sum of nb over sampled busy slots
+    // statistics outputs, zeroed by the caller
+    int* delay_max = nullptr;       // (J)
+    int* late = nullptr;            // (J)
+    int* delay_hist = nullptr;      // (J, nbins)
+    int* stuck = nullptr;           // (J)
+    long long* stuck_age = nullptr; // (J)
+    long long* qlen_sum = nullptr;  // (node_col + N), as the three below
+    int* qlen_max = nullptr;
+    int* busy_slots = nullptr;
+    long long* nb_sum = nullptr;
 };
 
 DEV_INLINE int num_res(const Case& c) { return c.Eb + c.N; }
 DEV_INLINE int mask_words(int R) { return (R + 31) / 32; }
+
+// Histogram bin of a sojourn d >= 0: exact below 16, then eight sub-bins per
+// octave (sim/timeslot.py::delay_bin is the same function).
+DEV_INLINE int delay_bin(int d) {
+    if (d < 16) return d < 0 ? 0 : d;
+    int e = 4;
+    while ((d >> (e + 1)) != 0) ++e;            // e = floor(log2 d)
+    return 16 + 8 * (e - 4) + ((d >> (e - 3)) & 7);
+}
 
 // resource of leg `stage` of job j; -1 once the task has no legs left
 DEV_INLINE int leg_res(const Case& c, const State& st, int j, int stage) {
@@ -163,12 +204,18 @@ DEV_INLINE void init_jobs(const Case& c, State& st, int tid, int nt) {
 }
 
 // ---- init, part 2: empty queues, per-resource job chains, slot 0 staged --
+template <bool Stats = false>
 DEV_INLINE void init_queues(const Case& c, State& st, int tid, int nt) {
     const int R = num_res(c);
     for (int r = tid; r < R; r += nt) {
         st.head[r] = st.tail[r] = st.fhead[r] = st.ftgt0[r] = -1;
         st.fcnt[r] = 0;
         if (r < c.Eb) st.busy[r] = 0;
+        if constexpr (Stats) {
+            st.qlen[r] = st.qmax[r] = st.bslots[r] = 0;
+            st.qsum[r] = 0;
+            if (r < c.Eb) st.nbsum[r] = 0;
+        }
         int first = -1;
         for (int j = c.J - 1; j >= 0; --j)
             if (st.jres[j] == r) { st.jnext[j] = first; first = j; }
@@ -180,11 +227,13 @@ DEV_INLINE void init_queues(const Case& c, State& st, int tid, int nt) {
 }
 
 // ---- arrivals of slot t, then the busy snapshot ---------------------------
+template <bool Stats = false>
 DEV_INLINE void arrive(const Case& c, State& st, int t, int tid, int nt) {
     const int R = num_res(c);
     for (int w = tid; w < mask_words(R); w += nt) st.fmask[w] = 0u;
     for (int r = tid; r < R; r += nt) {
         int it = 0;
+        [[maybe_unused]] int added = 0;
         for (int j = st.jfirst[r]; j >= 0; j = st.jnext[j]) {
             if (j >= c.J || ++it > c.J) { st.misc[ERR] = E_BOUND; break; }
             const int k = st.arr[j];
@@ -201,16 +250,28 @@ DEV_INLINE void arrive(const Case& c, State& st, int t, int tid, int nt) {
                 st.rem[q] = units;
                 append(st, r, q);
             }
+            if constexpr (Stats) added += k;
         }
         if (r < c.Eb) st.busy[r] = st.head[r] >= 0;
+        if constexpr (Stats) {          // the sample: arrivals in, none served
+            const int len = st.qlen[r] + added;
+            if (added) st.qlen[r] = len;
+            if (t >= c.warmup && len > 0) {
+                st.qsum[r] += len;
+                if (len > st.qmax[r]) st.qmax[r] = len;
+                st.bslots[r] += 1;
+            }
+        }
     }
 }
 
 // ---- service: every resource drains its own FIFO --------------------------
+template <bool Stats = false>
 DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
     const int R = num_res(c);
     for (int r = tid; r < R; r += nt) {
         int fh = -1, ft = -1, ftg = -1, nf = 0;
+        [[maybe_unused]] int popped = 0;
         int q = st.head[r];
         if (q >= 0) {
             double cap;
@@ -221,6 +282,8 @@ DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
                     if (o < 0 || o >= c.Eb) { st.misc[ERR] = E_INPUT; break; }
                     nb += st.busy[o];
                 }
+                if constexpr (Stats)
+                    if (t >= c.warmup) st.nbsum[r] += nb;
                 cap = (double)c.rates[r] / (1.0 + (double)nb);
             } else {
                 cap = (double)c.bw[r - c.Eb];
@@ -239,12 +302,24 @@ DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
                 if (j < 0 || j >= c.J) { st.misc[ERR] = E_POOL; break; }
                 const int stage = st.stage[q] + 1;
                 st.stage[q] = stage;
+                if constexpr (Stats) ++popped;
                 const int nr = leg_res(c, st, j, stage);
                 if (nr < 0) {                       // no legs left
                     const int t0 = st.t0[q];
                     if (t0 >= c.warmup) {
                         st.delay_sum[j] += (long long)(t + 1 - t0);
                         st.count[j] += 1;
+                        if constexpr (Stats) {
+                            const int d = t + 1 - t0;
+                            const int k = delay_bin(d);
+                            if (d < 0 || k >= c.nbins) {
+                                st.misc[ERR] = E_POOL;
+                                break;
+                            }
+                            if (d > st.delay_max[j]) st.delay_max[j] = d;
+                            if (d > c.late_after) st.late[j] += 1;
+                            st.delay_hist[(size_t)j * c.nbins + k] += 1;
+                        }
                     }
                     TSIM_COUNT_ADD(&st.misc[DEP], 1);
                 } else if (nr >= R) {
@@ -262,6 +337,8 @@ DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
             }
             st.head[r] = q;
             if (q < 0) st.tail[r] = -1;
+            if constexpr (Stats)
+                if (popped) st.qlen[r] -= popped;
         }
         st.fhead[r] = fh;
         st.ftgt0[r] = ftg;
@@ -271,10 +348,12 @@ DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
 }
 
 // ---- hand-over: finished tasks join their next queue, oracle order --------
+template <bool Stats = false>
 DEV_INLINE void handover(const Case& c, State& st, int t, int tid, int nt) {
     const int R = num_res(c);
     for (int r = tid; r < R; r += nt) {
         int it = 0;
+        [[maybe_unused]] int added = 0;
         bool stop = false;
         // sources with something to hand over, ascending: the set bits
         for (int w = 0; w < mask_words(R) && !stop; ++w) {
@@ -292,7 +371,10 @@ DEV_INLINE void handover(const Case& c, State& st, int t, int tid, int nt) {
                     if (++it > c.P) {
                         st.misc[ERR] = E_BOUND; stop = true; break;
                     }
-                    if (tg == r) append(st, r, q);
+                    if (tg == r) {
+                        append(st, r, q);
+                        if constexpr (Stats) ++added;
+                    }
                     if (i + 1 < n) {
                         q = st.fnext[q];
                         if (q < 0 || q >= c.P) {
@@ -303,6 +385,8 @@ DEV_INLINE void handover(const Case& c, State& st, int t, int tid, int nt) {
                 }
             }
         }
+        if constexpr (Stats)
+            if (added) st.qlen[r] += added;
     }
     if (tid == 0) {
         const int arrived = c.slot_off[t + 1] - c.slot_off[t];
@@ -317,6 +401,44 @@ DEV_INLINE void handover(const Case& c, State& st, int t, int tid, int nt) {
         }
     }
     if (t + 1 < c.T) stage_arrivals(c, st, t + 1, tid, nt);
+}
+
+// ---- statistics, after the last slot: the tasks still in the network ------
+// Threads stride over the pool; a task is unfinished iff it has a leg left.
+// Integer sums commute, so the adds may land in any order.
+DEV_INLINE void tally_backlog(const Case& c, State& st, int tid, int nt) {
+    const int used = c.slot_off[c.T];
+    if (used < 0 || used > c.P) {
+        if (tid == 0) st.misc[ERR] = E_POOL;
+        return;
+    }
+    for (int q = tid; q < used; q += nt) {
+        const int j = st.job[q];
+        const int stage = st.stage[q];
+        const int t0 = st.t0[q];
+        if (j < 0 || j >= c.J || stage < 0 || t0 < 0 || t0 >= c.T) {
+            st.misc[ERR] = E_POOL;
+            break;
+        }
+        if (t0 < c.warmup || leg_res(c, st, j, stage) < 0) continue;
+        TSIM_COUNT_ADD(&st.stuck[j], 1);
+        TSIM_COUNT_ADD64(&st.stuck_age[j], (long long)(c.T - t0));
+    }
+}
+
+// ---- statistics: the per-resource accumulators leave for their columns ----
+// Link l goes to column l, node v to column node_col + v: the outputs are
+// laid out by the batch's largest link count, not by this graph's Eb.
+DEV_INLINE void store_resource_stats(const Case& c, State& st, int tid,
+                                     int nt) {
+    const int R = num_res(c);
+    for (int r = tid; r < R; r += nt) {
+        const int col = r < c.Eb ? r : c.node_col + (r - c.Eb);
+        st.qlen_sum[col] = st.qsum[r];
+        st.qlen_max[col] = st.qmax[r];
+        st.busy_slots[col] = st.bslots[r];
+        if (r < c.Eb) st.nb_sum[col] = st.nbsum[r];
+    }
 }
 
 }  // namespace tsim

@@ -48,8 +48,39 @@ def draw_arrivals(jobs: JobInstance, T: int, seed: int) -> np.ndarray:
     return rng.poisson(rates, size=(int(T), len(rates)))
 
 
+def delay_bin(d: int) -> int:
+    """Histogram bin of a sojourn ``d >= 0``: exact below 16, then eight
+    sub-bins per octave, so a bin is at most 12.5 % wide
+    (``tsim::delay_bin`` in ops/hip/timeslot_phases.h is the same
+    function)."""
+    d = int(d)
+    if d < 16:
+        return d
+    e = d.bit_length() - 1                      # floor(log2 d)
+    return 16 + 8 * (e - 4) + ((d >> (e - 3)) & 7)
+
+
+def delay_bin_upper(k: int) -> int:
+    """The largest sojourn that falls into bin ``k``."""
+    k = int(k)
+    if k < 16:
+        return k
+    e, s = 4 + (k - 16) // 8, (k - 16) % 8
+    return ((8 + s + 1) << (e - 3)) - 1
+
+
+def num_delay_bins(T: int) -> int:
+    """Bins of a ``T``-slot run: a sojourn cannot exceed ``T``."""
+    return delay_bin(T) + 1
+
+
+STAT_KEYS = ("delay_max", "late", "delay_hist", "stuck", "stuck_age",
+             "qlen_sum", "qlen_max", "busy_slots", "nb_sum")
+
+
 def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
-                    warmup: int = 0, trace: bool = False):
+                    warmup: int = 0, trace: bool = False,
+                    stats: bool = False, late_after=None):
     """The simulator loop over explicit routes — the contract of the batched
     HIP kernel (ops/hip/timeslot.hip), which reproduces it integer for
     integer.
@@ -59,7 +90,19 @@ def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
     (J, H) with job j's links in its first ``nhop[j]`` columns; ``arrivals``
     is (T, J) integer counts.  Returns ``(delay_sum int64 (J,), count int64
     (J,))`` over the tasks that arrived at ``t0 >= warmup`` and completed,
-    plus the trace dict with ``trace=True``."""
+    plus the trace dict with ``trace=True``.
+
+    ``stats=True`` appends a dict of integer arrays (``STAT_KEYS``).  Per
+    job, over the counted tasks with sojourn ``d``: ``delay_max`` int32,
+    ``late`` int32 (``d > late_after``, an int, default ``T``: never),
+    ``delay_hist`` int32 (J, ``num_delay_bins(T)``) over ``delay_bin(d)``;
+    after the last slot, over the tasks with ``t0 >= warmup`` still in the
+    network: ``stuck`` int32 and ``stuck_age`` int64, the sum of ``T - t0``.
+    Per resource (E + N,), link l at l and node v at E + v, over the slots
+    ``t >= warmup`` sampled after the slot's arrivals and before service:
+    ``qlen_sum`` int64, ``qlen_max`` int32, ``busy_slots`` int32 (FIFO not
+    empty) and, links only, ``nb_sum`` int64: the busy conflicting links
+    summed over the link's own busy slots."""
     arrivals = np.asarray(arrivals)
     T, J = arrivals.shape
     E, N = int(g.num_links), int(g.num_nodes)
@@ -88,6 +131,15 @@ def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
     tr_net = np.zeros(T, dtype=np.int64)
     in_network = 0
     rows = np.repeat(np.arange(E), np.diff(conf_indptr[:E + 1]))
+    if stats:
+        late_after = T if late_after is None else int(late_after)
+        delay_max = np.zeros(J, dtype=np.int32)
+        late = np.zeros(J, dtype=np.int32)
+        delay_hist = np.zeros((J, num_delay_bins(T)), dtype=np.int32)
+        qlen_sum = np.zeros(E + N, dtype=np.int64)
+        qlen_max = np.zeros(E + N, dtype=np.int32)
+        busy_slots = np.zeros(E + N, dtype=np.int32)
+        nb_sum = np.zeros(E + N, dtype=np.int64)
 
     def enqueue(task: _Task, t: int):
         while task.stage < len(legs[task.job]):
@@ -99,6 +151,11 @@ def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
         if task.t0 >= warmup:
             delay_sum[task.job] += t - task.t0
             count[task.job] += 1
+            if stats:
+                d = t - task.t0
+                delay_max[task.job] = max(delay_max[task.job], d)
+                late[task.job] += d > late_after
+                delay_hist[task.job, delay_bin(d)] += 1
 
     for t in range(T):
         # arrivals
@@ -115,6 +172,14 @@ def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
         busy = np.array([1 if q else 0 for q in link_q], dtype=np.int64)
         nb_busy = np.zeros(E)
         np.add.at(nb_busy, rows, busy[conf_indices])
+        if stats and t >= warmup:
+            for r, q in enumerate(link_q + node_q):
+                if q:
+                    qlen_sum[r] += len(q)
+                    qlen_max[r] = max(qlen_max[r], len(q))
+                    busy_slots[r] += 1
+                    if r < E:
+                        nb_sum[r] += int(nb_busy[r])
         finished = []
         for l in range(E):
             if not link_q[l]:
@@ -153,10 +218,24 @@ def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
                 tr_dep[min(t + 1, T - 1)] += 1
         tr_net[t] = in_network
 
+    out = (delay_sum, count)
     if trace:
-        return delay_sum, count, {"arrivals": tr_arr, "departures": tr_dep,
-                                  "pkts_in_network": tr_net}
-    return delay_sum, count
+        out += ({"arrivals": tr_arr, "departures": tr_dep,
+                 "pkts_in_network": tr_net},)
+    if stats:
+        stuck = np.zeros(J, dtype=np.int32)
+        stuck_age = np.zeros(J, dtype=np.int64)
+        for q in link_q + node_q:
+            for task in q:
+                if task.t0 >= warmup:
+                    stuck[task.job] += 1
+                    stuck_age[task.job] += T - task.t0
+        out += ({"delay_max": delay_max, "late": late,
+                 "delay_hist": delay_hist, "stuck": stuck,
+                 "stuck_age": stuck_age, "qlen_sum": qlen_sum,
+                 "qlen_max": qlen_max, "busy_slots": busy_slots,
+                 "nb_sum": nb_sum},)
+    return out
 
 
 def simulate(g: CaseGraph, jobs: JobInstance, flows: List[Flow],

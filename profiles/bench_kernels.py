@@ -10,7 +10,9 @@ Output: one JSON line per (config, stage) with mean µs over the timed reps.
 (B=256, N=100, load 0.15, T=1000): the bare kernel launch, the whole
 ``EpisodeEngine.simulate`` call, and the Python ``simulate_routes`` on a few
 of the same instances on this host's CPU (whose outputs must equal the
-kernel's), with the ratio per batch.
+kernel's), with the ratio per batch.  ``--config timeslot_stats`` is the
+same configuration through the statistics entry point (``timeslot_sim_stats``,
+``simulate(stats=True)``).
 
 ``--config fixedpoint`` times the three kernels that are little else than
 the contention fixed point (actor_head_fwd, actor_head_bwd, critic) on the
@@ -159,7 +161,7 @@ def bench_config(name, nodes, batch, gtype, distinct, reps):
 
 
 def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
-                   py_instances=4):
+                   py_instances=4, stats=False):
     import time
     from types import SimpleNamespace
 
@@ -169,7 +171,8 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
     from multihop_offload_amd.models.chebconv import ChebConvStack
     from multihop_offload_amd.harness.train_batched import build_training_cases
     from multihop_offload_amd.ops import dispatch
-    from multihop_offload_amd.sim.timeslot import simulate_routes
+    from multihop_offload_amd.sim.timeslot import (num_delay_bins,
+                                                   simulate_routes)
 
     cases = build_training_cases(nodes, batch, 16, 1000, 7, gtype="ba",
                                  workers=8)
@@ -180,7 +183,7 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
     jobs = eng.sample_jobs(load, gen)
     res = eng.baseline_episode(jobs)
     arr = eng.draw_arrivals(jobs, T_sim, gen)
-    sim = eng.simulate(jobs, res, arr)
+    sim = eng.simulate(jobs, res, arr, stats=stats)
     tasks = int(arr.sum())
 
     # the bare launch: the wrapper's prefix sums and error read left out
@@ -195,11 +198,19 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
             eng.k_conf_base, eng.k_conf_cols, eng.link_rates.contiguous(),
             eng.proc_bws.contiguous(), eng.T_arr.contiguous(), eng.k_E_arr,
             eng.k_N_arr, 0, pool, False)
-    out = ext.timeslot_sim(*args)
+    launch = ext.timeslot_sim
+    if stats:
+        args += (torch.floor(eng.T_arr).to(torch.int32),
+                 num_delay_bins(T_sim))
+        launch = ext.timeslot_sim_stats
+    out = launch(*args)
     assert not bool(out[2].any())
     assert torch.equal(out[0], sim.delay_sum)
-    kernel_us = timeit(lambda: ext.timeslot_sim(*args), reps)
-    call_us = timeit(lambda: eng.simulate(jobs, res, arr), reps)
+    if stats:
+        assert torch.equal(out[6], sim.stats.delay_hist)
+        assert torch.equal(out[9], sim.stats.qlen_sum)
+    kernel_us = timeit(lambda: launch(*args), reps)
+    call_us = timeit(lambda: eng.simulate(jobs, res, arr, stats=stats), reps)
 
     # the Python simulator on the first instances, same host, same inputs
     f64 = lambda x: x.cpu().numpy().astype(np.float64)   # noqa: E731
@@ -217,14 +228,27 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
              res.route_links[b, :k].cpu().numpy(),
              res.nhop[b, :k].cpu().numpy(), arr[b][:, :k].cpu().numpy())
         t0 = time.perf_counter()
-        ds, ct = simulate_routes(*a)
+        ds, ct, *st = simulate_routes(*a, stats=stats,
+                                      late_after=int(eng.T_arr[b]))
         t_py += time.perf_counter() - t0
+        if stats:
+            E = g.num_links
+            assert np.array_equal(st[0]["delay_hist"],
+                                  sim.stats.delay_hist[b, :k].cpu().numpy())
+            assert np.array_equal(st[0]["stuck_age"],
+                                  sim.stats.stuck_age[b, :k].cpu().numpy())
+            for key in ("qlen_sum", "qlen_max", "busy_slots", "nb_sum"):
+                got = getattr(sim.stats, key)[b].cpu().numpy()
+                assert np.array_equal(st[0][key][:E], got[:E]), key
+                assert np.array_equal(st[0][key][E:], got[eng.E:]), key
         assert np.array_equal(ds, sim.delay_sum[b, :k].cpu().numpy())
         assert np.array_equal(ct, sim.count[b, :k].cpu().numpy())
     py_s = t_py / py_instances
-    plan = dispatch.timeslot_lds_plan(eng.N, eng.E, eng.Jmax)
+    plan = (dispatch.timeslot_stats_lds_plan if stats
+            else dispatch.timeslot_lds_plan)(eng.N, eng.E, eng.Jmax)
     print(json.dumps({
-        "config": f"timeslot_b{batch}_n{nodes}", "stage": "timeslot_sim",
+        "config": f"timeslot_b{batch}_n{nodes}",
+        "stage": "timeslot_sim_stats" if stats else "timeslot_sim",
         "B": eng.B, "N": eng.N, "E": eng.E, "J": eng.Jmax, "T": T_sim,
         "load": load, "tasks": tasks, "pool": pool,
         "lds_bytes": plan["lds_bytes"], "threads": plan["threads"],
@@ -380,7 +404,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="both",
                     choices=["flagship", "er1000", "both", "timeslot",
-                             "fixedpoint", "apsp"])
+                             "timeslot_stats", "fixedpoint", "apsp"])
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--budgets", type=str, default="-1",
                     help="fixedpoint: staging budgets in bytes, comma-"
@@ -394,6 +418,8 @@ if __name__ == "__main__":
         bench_apsp(reps=max(args.reps, 200))
     if args.config == "timeslot":
         bench_timeslot(reps=args.reps)
+    if args.config == "timeslot_stats":
+        bench_timeslot(reps=args.reps, stats=True)
     if args.config in ("flagship", "both"):
         bench_config("flagship_b1024_n110", 110, 1024, "ba", 16, args.reps)
     if args.config in ("er1000", "both"):
