@@ -76,6 +76,17 @@ def queue_csr_force_global(on: bool) -> None:
     _require_hip().queue_csr_force_global(bool(on))
 
 
+def cheb_force_full_width(on: bool) -> None:
+    """Make every later forward of the K<=2 LDS-resident ChebConv kernels
+    (``ChebStackFn``, ``cheb_fwd_edge``) take the full-width path, which
+    pads the first and the last layer to 32 columns, instead of the
+    edge-layer path that serves a real output width of 1 (``False`` restores
+    the choice by width).  A host-side switch for before/after timings, the
+    edge-layer tests and bisecting; the backward follows its forward.
+    ``lam`` is bit-equal either way, the gradients agree to rounding."""
+    _require_hip().cheb_force_full_width(bool(on))
+
+
 # the statistics of timeslot_sim(stats=True), in the extension's order
 STAT_KEYS = ("delay_max", "late", "delay_hist", "stuck", "stuck_age",
              "qlen_sum", "qlen_max", "busy_slots", "nb_sum")

@@ -45,7 +45,10 @@ class ChebStackFn(torch.autograd.Function):
     """Fused L-layer ChebConv stack: x (B,Ē,4) → λ (B,Ē) with per-layer
     activations saved for the fused backward.  Dispatches between the
     LDS-resident kernel (ops/hip/chebconv.hip) and the row-tiled
-    large-graph kernels (ops/hip/chebconv_large.hip) by LDS fit."""
+    large-graph kernels (ops/hip/chebconv_large.hip) by LDS fit.  The K<=2
+    LDS-resident kernels are told the real output width and run the first
+    and last layer at their real width when it is 1
+    (``dispatch.cheb_force_full_width`` switches that off)."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, eng, *params):
@@ -58,6 +61,7 @@ class ChebStackFn(torch.autograd.Function):
             Wp, bp = pack_cheb_params(params)
         ctx.K = K
         ctx.large = not cheb_lds_fits(eng.Ee, K)
+        extra = ()
         if K > 2:
             # generic-K recurrence kernels (3 LDS row buffers); no
             # large-graph variant — refuse loudly rather than fall back
@@ -74,11 +78,14 @@ class ChebStackFn(torch.autograd.Function):
             lam, acts = ext.cheb_large_fwd(x, Wp, bp, eng.k_ext_indptr,
                                            eng.k_ext_base, eng.k_ext_cols)
         else:
-            lam, acts, t1s = ext.cheb_fwd(x, Wp, bp, eng.k_ext_indptr,
-                                          eng.k_ext_base, eng.k_ext_cols,
-                                          eng.k_ext_max_nnz)
+            # the real output width selects the edge-layer path (width 1);
+            # the launcher reports what it took and the backward follows
+            lam, acts, t1s, ctx.edge = ext.cheb_fwd_edge(
+                x, Wp, bp, eng.k_ext_indptr, eng.k_ext_base, eng.k_ext_cols,
+                eng.k_ext_max_nnz, params[-2].shape[2])
             ctx.t1s = t1s
-        ctx.save_for_backward(acts, Wp)
+            extra = (x, lam)       # what the edge-layer backward reads
+        ctx.save_for_backward(acts, Wp, *extra)
         ctx.eng = eng
         ctx.shapes = [tuple(p.shape) for p in params]
         ctx.params = params
@@ -86,7 +93,7 @@ class ChebStackFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlam: torch.Tensor):
-        acts, Wp = ctx.saved_tensors
+        acts, Wp, *x_lam = ctx.saved_tensors
         eng = ctx.eng
         ext = dispatch.require_hip()
         if ctx.K > 2:
@@ -98,9 +105,10 @@ class ChebStackFn(torch.autograd.Function):
                                         eng.k_ext_indptr, eng.k_ext_base,
                                         eng.k_ext_cols)
         else:
-            dW, db = ext.cheb_bwd(dlam.contiguous(), acts, ctx.t1s, Wp,
-                                  eng.k_ext_indptr, eng.k_ext_base,
-                                  eng.k_ext_cols, eng.k_ext_max_nnz)
+            dW, db = ext.cheb_bwd_edge(dlam.contiguous(), *x_lam, acts,
+                                       ctx.t1s, Wp, eng.k_ext_indptr,
+                                       eng.k_ext_base, eng.k_ext_cols,
+                                       eng.k_ext_max_nnz, ctx.edge)
         if getattr(eng, "per_sample_request", False):
             eng._per_sample_raw = (dW, db)   # per-graph partials, pre-sum
         if ctx.native:

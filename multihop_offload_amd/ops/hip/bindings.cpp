@@ -114,6 +114,21 @@ std::vector<torch::Tensor> cheb_kn_bwd_hip(
     torch::Tensor W, torch::Tensor ext_indptr, torch::Tensor ext_base,
     torch::Tensor ext_cols, long max_nnz);
 bool cheb_fits_lds(long Ee, long K);
+void cheb_force_full_width(bool on);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, bool>
+cheb_fwd_edge_hip(torch::Tensor x, torch::Tensor W, torch::Tensor bias,
+                  torch::Tensor ext_indptr, torch::Tensor ext_base,
+                  torch::Tensor ext_cols, long max_nnz, long out_width);
+std::vector<torch::Tensor> cheb_bwd_edge_hip(
+    torch::Tensor dlam, torch::Tensor x, torch::Tensor lam,
+    torch::Tensor acts, torch::Tensor t1s, torch::Tensor W,
+    torch::Tensor ext_indptr, torch::Tensor ext_base,
+    torch::Tensor ext_cols, long max_nnz, bool edge);
+std::vector<torch::Tensor> cheb_bwd_edge_hip_mask(
+    torch::Tensor dlam, torch::Tensor x, torch::Tensor lam,
+    torch::Tensor acts, torch::Tensor t1s, torch::Tensor W,
+    torch::Tensor ext_indptr, torch::Tensor ext_base,
+    torch::Tensor ext_cols, long max_nnz, bool edge, long stage_mask);
 
 std::vector<torch::Tensor> cheb_large_fwd_hip(
     torch::Tensor x, torch::Tensor W, torch::Tensor bias,
@@ -156,6 +171,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("cheb_fwd", &cheb_fwd_hip);
     m.def("cheb_bwd", &cheb_bwd_hip);
     m.def("cheb_bwd_ablate", &cheb_bwd_hip_mask);
+    m.def("cheb_force_full_width", &cheb_force_full_width);
+    m.def("cheb_fwd_edge", &cheb_fwd_edge_hip);
+    m.def("cheb_bwd_edge", &cheb_bwd_edge_hip);
+    m.def("cheb_bwd_edge_ablate", &cheb_bwd_edge_hip_mask);
     m.def("cheb_kn_fwd", &cheb_kn_fwd_hip);
     m.def("cheb_kn_bwd", &cheb_kn_bwd_hip);
     m.def("cheb_fits_lds", &cheb_fits_lds);

@@ -65,10 +65,27 @@ DEV_INLINE void gemm_rows(const float* __restrict__ src,
 }
 
 // ---- weight-gradient tile: dW[i][j] += sum_r src[r][i] * delta[r][j] -----
-// MFMA over the row (K) dimension: 2×2 output tiles of 16×16, each over
-// SPLIT equal row ranges (rows a multiple of 4*SPLIT); one (tile, range)
-// per wave.  The ranges and the row tiles of a graph combine through global
-// fp32 atomics (dW is prezeroed).
+// MFMA over the row (K) dimension.  wgrad_tile: one wave's 16×16 tile at
+// (i0, j0) over the row k-steps [kk0, kk1) (4 rows each), C layout as in
+// gemm_rows.
+DEV_INLINE f32x4 wgrad_tile(const float* __restrict__ src,
+                            const float* __restrict__ delta, int i0, int j0,
+                            int kk0, int kk1, int lane) {
+    const int k_in = lane >> 4;
+    const int c_in = lane & 15;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int kk = kk0; kk < kk1; ++kk) {
+        const int r = kk * 4 + k_in;
+        const float a = src[r * STRIDE + i0 + c_in];
+        const float b = delta[r * STRIDE + j0 + c_in];
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// 2×2 output tiles of 16×16, each over SPLIT equal row ranges (rows a
+// multiple of 4*SPLIT); one (tile, range) per wave.  The ranges and the row
+// tiles of a graph combine through global fp32 atomics (dW is prezeroed).
 template <int SPLIT>
 DEV_INLINE void wgrad_rows(const float* __restrict__ src,
                            const float* __restrict__ delta,
@@ -77,20 +94,12 @@ DEV_INLINE void wgrad_rows(const float* __restrict__ src,
     const int lane = tid & 63;
     const int wid = tid >> 6;
     const int nw = blockDim.x >> 6;
-    const int k_in = lane >> 4;
-    const int c_in = lane & 15;
     for (int t = wid; t < 4 * SPLIT; t += nw) {
         const int tile = t / SPLIT, part = t % SPLIT;
         const int i0 = (tile >> 1) * 16, j0 = (tile & 1) * 16;
         const int kk0 = part * (rows / (4 * SPLIT));
         const int kk1 = kk0 + rows / (4 * SPLIT);
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int kk = kk0; kk < kk1; ++kk) {
-            const int r = kk * 4 + k_in;
-            const float a = src[r * STRIDE + i0 + c_in];
-            const float b = delta[r * STRIDE + j0 + c_in];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-        }
+        const f32x4 acc = wgrad_tile(src, delta, i0, j0, kk0, kk1, lane);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             atomicAdd(&dw_out[(i0 + (lane >> 4) * 4 + r) * F + j0

@@ -13,8 +13,29 @@
 // per-layer activations, per-graph dW/db partials (summed over the batch by
 // torch), dX propagated through W0ᵀ and the symmetric SpMV.
 //
-// Feature dims are padded to 32 (layer-0 input 4→32, output 1→32 with
-// zero-padded weights; padding is exact — zero rows/cols contribute 0).
+// Feature dims are padded to 32 in the weight and gradient layouts
+// (layer-0 input 4→32, output 1→32 with zero-padded weights; padding is
+// exact — zero rows/cols contribute 0).
+//
+// Edge layers.  When the caller states a real output width of 1
+// (cheb_fwd_edge / cheb_bwd_edge, L >= 2) the K<=2 kernels do the first and
+// the last layer at their real width instead of working on the zeros:
+//   forward, layer 0: a 4-column SpMV and one MFMA k-step per Chebyshev
+//     term (the skipped terms are exact zeros, the k order is kept, so the
+//     sums are bitwise those of the full-width path); T1_0 is saved 4 wide
+//     at the head of t1s slot 0; no acts[0] store.
+//   forward, last layer: only the c0 = 0 tile; lam goes from the MFMA
+//     registers to memory; no acts[L] store.
+//   backward, last layer: ReLU mask from lam; db of one column; both terms'
+//     weight gradients in one pass over the two live tiles each (term ×
+//     tile × row half = 8 waves, still two atomic addends per cell);
+//     dX = d⊗w0 + (A·d)⊗w1 with a one-column gather — no MFMA product, no
+//     32-column SpMV.
+//   backward, layer 0: X_0 from x and T1_0 4 wide; weight gradients as in
+//     the last layer, over the i0 = 0 tiles.
+// dW / db cells outside the real shapes are never written and stay the
+// zeros of the prezeroed buffers.  Any other width, the old entry points
+// and cheb_force_full_width(true) run the full-width path.
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -254,10 +275,238 @@ DEV_INLINE void load_top_delta(float* __restrict__ Db,
     }
 }
 
+// ---- edge layers at their real width (header comment) --------------------
+constexpr int FIN = 4;           // real input width of layer 0
+
+// buf[:, 0:cols] <- a dense (Ee, 4) matrix in columns 0..3, zeros in the
+// other columns and in the padded rows.  cols = 4 feeds the forward (which
+// reads 4 columns), cols = 16 one wgrad tile.
+DEV_INLINE void load_rows4(float* __restrict__ buf,
+                           const float* __restrict__ g4, int cols, int Ee,
+                           int rows_pad, int tid, int nt) {
+    for (int r = tid; r < rows_pad; r += nt) {
+        float* row = buf + r * STRIDE;
+        float4 v = {0.f, 0.f, 0.f, 0.f};
+        if (r < Ee) v = *reinterpret_cast<const float4*>(g4 + (size_t)r * 4);
+        row[0] = v.x; row[1] = v.y; row[2] = v.z; row[3] = v.w;
+        for (int c = FIN; c < cols; ++c) row[c] = 0.f;
+    }
+}
+
+// dst[r][0:4] = (A·src)[r][0:4]: the neighbour loop of spmv (pairs, two
+// accumulators), so the sums are bitwise its columns 0..3
+DEV_INLINE void spmv4(const float* __restrict__ src, float* __restrict__ dst,
+                      const int* __restrict__ indptr,
+                      const int* __restrict__ cols, int Ee, int rows_pad,
+                      int tid, int nt) {
+    for (int r = tid; r < rows_pad; r += nt) {
+        float acc[FIN] = {0, 0, 0, 0};
+        if (r < Ee) {
+            int a = indptr[r];
+            const int end = indptr[r + 1];
+            float acc1[FIN] = {0, 0, 0, 0};
+            for (; a + 3 < end; a += 4) {
+                const float* s0 = src + cols[a] * STRIDE;
+                const float* s1 = src + cols[a + 1] * STRIDE;
+                const float* s2 = src + cols[a + 2] * STRIDE;
+                const float* s3 = src + cols[a + 3] * STRIDE;
+#pragma unroll
+                for (int c = 0; c < FIN; ++c) {
+                    acc[c] += s0[c] + s1[c];
+                    acc1[c] += s2[c] + s3[c];
+                }
+            }
+            for (; a < end; ++a) {
+                const float* s = src + cols[a] * STRIDE;
+#pragma unroll
+                for (int c = 0; c < FIN; ++c) acc[c] += s[c];
+            }
+#pragma unroll
+            for (int c = 0; c < FIN; ++c) acc[c] += acc1[c];
+        }
+#pragma unroll
+        for (int c = 0; c < FIN; ++c) dst[r * STRIDE + c] = acc[c];
+    }
+}
+
+// Layer 0: Xb <- act(X[:, 0:4]·W0[0:4] + T[:, 0:4]·W1[0:4] + b), the kk = 0
+// steps of gemm_layer_fused in its order.  One wave owns both column halves
+// of a row tile: it has read its A operands before it writes, and no other
+// wave reads those rows.
+DEV_INLINE void gemm_layer_first(float* __restrict__ Xb,
+                                 const float* __restrict__ Tb,
+                                 const float* __restrict__ Wl,
+                                 const float* __restrict__ bl, int K,
+                                 int rows_pad, int tid) {
+    const int lane = tid & 63;
+    const int wid = tid >> 6;
+    const int nw = blockDim.x >> 6;
+    const int r_in = lane & 15;
+    const int k_in = lane >> 4;
+    for (int mt = wid; mt < rows_pad / 16; mt += nw) {
+        const float ax = Xb[(mt * 16 + r_in) * STRIDE + k_in];
+        const float at = K > 1 ? Tb[(mt * 16 + r_in) * STRIDE + k_in] : 0.f;
+        f32x4 acc[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+            acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                ax, Wl[k_in * F + h * 16 + r_in], zero, 0, 0, 0);
+            if (K > 1)
+                acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                    at, Wl[F * F + k_in * F + h * 16 + r_in], acc[h], 0, 0,
+                    0);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int col = h * 16 + (lane & 15);
+            const float bv = bl[col];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = mt * 16 + (lane >> 4) * 4 + r;
+                Xb[row * STRIDE + col] = act(acc[h][r] + bv, false);
+            }
+        }
+    }
+}
+
+// Last layer of real width 1: the c0 = 0 tile of gemm_layer_fused, column 0
+// of it written straight to lam
+DEV_INLINE void gemm_layer_last(const float* __restrict__ Xb,
+                                const float* __restrict__ Tb,
+                                const float* __restrict__ Wl,
+                                const float* __restrict__ bl,
+                                float* __restrict__ lam, int K, int Ee,
+                                int rows_pad, int tid) {
+    const int lane = tid & 63;
+    const int wid = tid >> 6;
+    const int nw = blockDim.x >> 6;
+    const int r_in = lane & 15;
+    const int k_in = lane >> 4;
+    for (int mt = wid; mt < rows_pad / 16; mt += nw) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < F / 4; ++kk) {
+            const int k = kk * 4 + k_in;
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                Xb[(mt * 16 + r_in) * STRIDE + k], Wl[k * F + r_in], acc, 0,
+                0, 0);
+        }
+        if (K > 1) {
+#pragma unroll
+            for (int kk = 0; kk < F / 4; ++kk) {
+                const int k = kk * 4 + k_in;
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                    Tb[(mt * 16 + r_in) * STRIDE + k],
+                    Wl[F * F + k * F + r_in], acc, 0, 0, 0);
+            }
+        }
+        if ((lane & 15) == 0) {
+            const float bv = bl[0];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = mt * 16 + (lane >> 4) * 4 + r;
+                if (row < Ee) lam[row] = act(acc[r] + bv, true);
+            }
+        }
+    }
+}
+
+// Db[:, 0:16] <- top delta with the ReLU mask of the last layer: column 0
+// is dλ where lam > 0 (lam == nullptr: unmasked), the rest of the one live
+// wgrad tile zero
+DEV_INLINE void load_top_delta_edge(float* __restrict__ Db,
+                                    const float* __restrict__ dlamb,
+                                    const float* __restrict__ lamb, int Ee,
+                                    int rows_pad, int tid, int nt) {
+    for (int r = tid; r < rows_pad; r += nt) {
+        float* row = Db + r * STRIDE;
+        float d = 0.f;
+        if (r < Ee) d = dlamb[r] * (lamb ? dact(lamb[r], 0.f) : 1.f);
+        row[0] = d;
+        for (int c = 1; c < 16; ++c) row[c] = 0.f;
+    }
+}
+
+// db[0] = sum_r D[r][0]: one wave, one plain store (db is prezeroed and the
+// cell has this one writer)
+DEV_INLINE void db_col0(const float* __restrict__ D, int rows,
+                        float* __restrict__ db_out, int tid) {
+    if (tid >= 64) return;
+    float acc = 0.f;
+    for (int r = tid; r < rows; r += 64) acc += D[r * STRIDE];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (tid == 0) db_out[0] = acc;
+}
+
+// Weight gradients of an edge layer, both Chebyshev terms in one pass.
+// Only the i0 = 0 tiles (layer 0, `first`) or the j0 = 0 tiles (last layer)
+// are live: term × live tile × row half is one task per wave, and each cell
+// still gets two atomic addends onto zero, which commute — dW stays
+// run-to-run deterministic.  Cells outside the real shape are not written.
+DEV_INLINE void wgrad_edge(const float* __restrict__ Xs,
+                           const float* __restrict__ Ts,
+                           const float* __restrict__ delta,
+                           float* __restrict__ dw_out,  // global [K][32][32]
+                           int K, bool first, int rows, int tid) {
+    const int lane = tid & 63;
+    const int wid = tid >> 6;
+    const int nw = blockDim.x >> 6;
+    const int n = rows / (4 * WGRAD_SPLIT);
+    for (int t = wid; t < 2 * WGRAD_SPLIT * K; t += nw) {
+        const int k = t / (2 * WGRAD_SPLIT);
+        const int o = ((t / WGRAD_SPLIT) & 1) * 16;
+        const int part = t % WGRAD_SPLIT;
+        const int i0 = first ? 0 : o, j0 = first ? o : 0;
+        const f32x4 acc = wgrad_tile(k ? Ts : Xs, delta, i0, j0, part * n,
+                                     part * n + n, lane);
+        if (first ? (lane >> 4) == 0 : (lane & 15) == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                atomicAdd(&dw_out[(size_t)k * F * F +
+                                  (i0 + (lane >> 4) * 4 + r) * F + j0 +
+                                  (lane & 15)], acc[r]);
+        }
+    }
+}
+
+// Last layer's dX = d⊗w0 + (A·d)⊗w1 into Ab, d = Db[:, 0]; wv = w0 | w1,
+// column 0 of W_0 and W_1.  parts (timing ablation): bit0 the d⊗w0 term,
+// bit1 the gather.
+DEV_INLINE void dx_rank1(const float* __restrict__ Db, float* __restrict__ Ab,
+                         const float* __restrict__ wv,
+                         const int* __restrict__ indptr,
+                         const int* __restrict__ cols, int Ee, int rows_pad,
+                         int K, int parts, int tid, int nt) {
+    for (int r = tid; r < rows_pad; r += nt) {
+        const float dv = (parts & 1) ? Db[r * STRIDE] : 0.f;
+        float ad = 0.f;
+        if ((parts & 2) && K > 1 && r < Ee) {
+            int a = indptr[r];
+            const int end = indptr[r + 1];
+            float ad1 = 0.f;
+            for (; a + 3 < end; a += 4) {
+                ad += Db[cols[a] * STRIDE] + Db[cols[a + 1] * STRIDE];
+                ad1 += Db[cols[a + 2] * STRIDE] + Db[cols[a + 3] * STRIDE];
+            }
+            for (; a < end; ++a) ad += Db[cols[a] * STRIDE];
+            ad += ad1;
+        }
+        float* o = Ab + r * STRIDE;
+#pragma unroll
+        for (int c = 0; c < F; ++c)
+            o[c] = dv * wv[c] + (K > 1 ? ad * wv[F + c] : 0.f);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // forward: x (B,Ee,4) → lam (B,Ee); saves per-layer activations
-// LDS: Xb | Tb | Yb (rows_pad*STRIDE each) | Wl (K*32*32) | bias (32)
+// LDS: Xb | Tb (rows_pad*STRIDE each) | Wl (K*32*32) | bias (32) | CSR
+// EDGE: first and last layer at their real width (needs L >= 2): acts
+// slots 0 and L are not written, t1s slot 0 holds T1_0 as (Ee,4)
 // ---------------------------------------------------------------------------
+template <bool EDGE>
 __global__ void cheb_fwd_kernel(
     const float* __restrict__ x_in,      // (B,Ee,4)
     const float* __restrict__ W,         // (L,K,32,32) padded
@@ -282,11 +531,38 @@ __global__ void cheb_fwd_kernel(
               reinterpret_cast<int*>(bl + F), tid, nt, ipt, cls);
     float* actsb = acts + (size_t)b * (L + 1) * Ee * F;
 
-    load_features(Xb, x_in + (size_t)b * Ee * 4, Ee, rows_pad, tid, nt);
-    __syncthreads();
-    store_rows(Xb, actsb, 0, Ee, Ee, tid, nt);
+    if (EDGE) {
+        // ---- layer 0 at its real width: 4 columns in, rows 0..3 of W_k
+        load_rows4(Xb, x_in + (size_t)b * Ee * 4, FIN, Ee, rows_pad, tid,
+                   nt);
+        for (int i = tid; i < K * FIN * F; i += nt)
+            Wl[(i / (FIN * F)) * F * F + i % (FIN * F)] =
+                W[(size_t)(i / (FIN * F)) * F * F + i % (FIN * F)];
+        for (int i = tid; i < F; i += nt) bl[i] = bias[i];
+        __syncthreads();
+        if (K > 1) {
+            spmv4(Xb, Tb, ipt, cls, Ee, rows_pad, tid, nt);
+            __syncthreads();
+            // T1_0, 4 wide, at the head of its t1s slot
+            float4* t1b =
+                reinterpret_cast<float4*>(t1s + (size_t)b * L * Ee * F);
+            for (int r = tid; r < Ee; r += nt) {
+                const float* s = Tb + r * STRIDE;
+                t1b[r] = make_float4(s[0], s[1], s[2], s[3]);
+            }
+        }
+        gemm_layer_first(Xb, Tb, Wl, bl, K, rows_pad, tid);
+        __syncthreads();
+        store_rows(Xb, actsb + (size_t)Ee * F, 0, Ee, Ee, tid, nt);
+        __syncthreads();
+    } else {
+        load_features(Xb, x_in + (size_t)b * Ee * 4, Ee, rows_pad, tid, nt);
+        __syncthreads();
+        store_rows(Xb, actsb, 0, Ee, Ee, tid, nt);
+    }
 
-    for (int l = 0; l < L; ++l) {
+    // the full-width layers: all of them, or all but the two edge layers
+    for (int l = EDGE ? 1 : 0; l < (EDGE ? L - 1 : L); ++l) {
         // stage weights + bias
         for (int i = tid; i < K * F * F; i += nt)
             Wl[i] = W[((size_t)l * K) * F * F + i];
@@ -306,8 +582,26 @@ __global__ void cheb_fwd_kernel(
                    tid, nt);
         __syncthreads();
     }
-    for (int r = tid; r < Ee; r += nt) lam[(size_t)b * Ee + r] =
-        Xb[r * STRIDE];
+
+    if (EDGE) {
+        // ---- last layer at its real width: one output column
+        const int l = L - 1;
+        for (int i = tid; i < K * F * F; i += nt)
+            Wl[i] = W[((size_t)l * K) * F * F + i];
+        if (tid == 0) bl[0] = bias[l * F];
+        __syncthreads();
+        if (K > 1) {
+            spmv(Xb, Tb, ipt, cls, Ee, rows_pad, tid, nt, 0);
+            __syncthreads();
+            store_rows(Tb, t1s + ((size_t)b * L + l) * Ee * F, 0, Ee, Ee,
+                       tid, nt);
+        }
+        gemm_layer_last(Xb, Tb, Wl, bl, lam + (size_t)b * Ee, K, Ee,
+                        rows_pad, tid);
+    } else {
+        for (int r = tid; r < Ee; r += nt) lam[(size_t)b * Ee + r] =
+            Xb[r * STRIDE];
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -317,8 +611,14 @@ __global__ void cheb_fwd_kernel(
 // ---------------------------------------------------------------------------
 // stage_mask (timing ablation only — outputs are wrong unless 0xF):
 // bit0 act-mask+db, bit1 load_rows+wgrads, bit2 dx gemm, bit3 spmv
+// EDGE: the backward of the EDGE forward (x_in, lam and its acts / t1s), on
+// the LDS plan of the full-width one.  On the last layer bit2 is the d⊗w0
+// term and bit3 the one-column gather of dx_rank1.
+template <bool EDGE>
 __global__ void cheb_bwd_kernel(
     const float* __restrict__ dlam,      // (B,Ee)
+    const float* __restrict__ x_in,      // (B,Ee,4)   (EDGE only)
+    const float* __restrict__ lam,       // (B,Ee)     (EDGE only)
     const float* __restrict__ acts,      // (B,L+1,Ee,32)
     const float* __restrict__ t1s,       // (B,L,Ee,32): A·X from forward
     const float* __restrict__ W,         // (L,K,32,32)
@@ -344,10 +644,42 @@ __global__ void cheb_bwd_kernel(
     float* dWb = dW + (size_t)b * L * K * F * F;
     float* dbb = db + (size_t)b * L * F;
 
-    load_top_delta(Db, dlam + (size_t)b * Ee, Ee, rows_pad, tid, nt);
-    __syncthreads();
+    if (EDGE) {
+        // ---- last layer: the delta has one live column
+        const int l = L - 1;
+        load_top_delta_edge(Db, dlam + (size_t)b * Ee,
+                            (stage_mask & 1) ? lam + (size_t)b * Ee : nullptr,
+                            Ee, rows_pad, tid, nt);
+        if (stage_mask & 2) {
+            load_rows(Ab, actsb + (size_t)l * Ee * F, 0, rows_pad, Ee, tid,
+                      nt);
+            if (K > 1)
+                load_rows(Tb, t1s + ((size_t)b * L + l) * Ee * F, 0,
+                          rows_pad, Ee, tid, nt);
+        }
+        // w0 | w1: column 0 of W_0 and W_1
+        for (int i = tid; i < K * F; i += nt)
+            Wl[i] = W[(((size_t)l * K + i / F) * F + i % F) * F];
+        __syncthreads();
+        if (stage_mask & 1) db_col0(Db, Ee, dbb + l * F, tid);
+        if (stage_mask & 2)
+            wgrad_edge(Ab, Tb, Db, dWb + ((size_t)l * K) * F * F, K, false,
+                       rows_pad, tid);
+        __syncthreads();
+        if (stage_mask & 12)
+            dx_rank1(Db, Ab, Wl, ipt, cls, Ee, rows_pad, K,
+                     (stage_mask >> 2) & 3, tid, nt);
+        __syncthreads();
+        float* tmp = Ab;
+        Ab = Db;
+        Db = tmp;
+    } else {
+        load_top_delta(Db, dlam + (size_t)b * Ee, Ee, rows_pad, tid, nt);
+        __syncthreads();
+    }
 
-    for (int l = L - 1; l >= 0; --l) {
+    // the full-width layers: all of them, or all but the two edge layers
+    for (int l = EDGE ? L - 2 : L - 1; l >= (EDGE ? 1 : 0); --l) {
         const bool last = (l == L - 1);
         // activation mask from stored post-act X_{l+1} (coalesced float4)
         if (stage_mask & 1)
@@ -358,9 +690,14 @@ __global__ void cheb_bwd_kernel(
         // ~400-cycle loads; and folding db into the mask sweep above was
         // measured +13% — atomic flush every column-group change.
         // profiles/r02_notes.md: measure, don't guess.)
-        if (stage_mask & 2)
-            load_rows(Ab, actsb + (size_t)l * Ee * F, 0, rows_pad, Ee, tid,
+        if (stage_mask & 2) {
+            if (EDGE)
+                load_rows(Ab, actsb + (size_t)l * Ee * F, 0, rows_pad, Ee, tid,
                       nt);
+            else
+                load_rows(Ab, actsb + (size_t)l * Ee * F, 0, rows_pad, Ee,
+                          tid, nt);
+        }
         for (int i = tid; i < K * F * F; i += nt)
             Wl[i] = W[((size_t)l * K) * F * F + i];
         __syncthreads();
@@ -397,7 +734,24 @@ __global__ void cheb_bwd_kernel(
         float* tmp = Ab;
         Ab = Db;
         Db = tmp;
+        if (!EDGE) __syncthreads();
+    }
+
+    if (EDGE) {
+        // ---- layer 0: X_0 = x and T1_0, 4 wide; db, the i0 = 0 tiles of dW
+        if (stage_mask & 1)
+            mask_rows(Db, actsb + (size_t)Ee * F, Ee, 0.2f, tid, nt);
+        if (stage_mask & 2) {
+            load_rows4(Ab, x_in + (size_t)b * Ee * 4, 16, Ee, rows_pad, tid,
+                       nt);
+            if (K > 1)
+                load_rows4(Tb, t1s + (size_t)b * L * Ee * F, 16, Ee,
+                           rows_pad, tid, nt);
+        }
         __syncthreads();
+        if (stage_mask & 1) db_colsum(Db, Ee, dbb, tid, nt);
+        if (stage_mask & 2)
+            wgrad_edge(Ab, Tb, Db, dWb, K, true, rows_pad, tid);
     }
 }
 
@@ -579,21 +933,30 @@ bool cheb_fits_lds(long Ee, long K) {
            cheb_lds_plan(Ee, K, kn ? KN_NBUF : BWD_NBUF, false, 0).fits;
 }
 
-std::vector<torch::Tensor> cheb_fwd_hip(
+// cheb_force_full_width(true): every later cheb_fwd_edge launch takes the
+// full-width path whatever the stated width (before/after timings, tests,
+// bisecting); false restores the choice by width.  Read when the forward is
+// launched; the backward follows the flag its forward returned.
+static bool cheb_full_forced = false;
+void cheb_force_full_width(bool on) { cheb_full_forced = on; }
+
+static std::vector<torch::Tensor> cheb_fwd_launch(
     torch::Tensor x, torch::Tensor W, torch::Tensor bias,
     torch::Tensor ext_indptr, torch::Tensor ext_base,
-    torch::Tensor ext_cols, long max_nnz) {
+    torch::Tensor ext_cols, long max_nnz, bool edge) {
     const int B = x.size(0), Ee = x.size(1);
     const int L = W.size(0), K = W.size(1);
     TORCH_CHECK(K <= 2, "fused ChebConv kernel supports K<=2");
+    TORCH_CHECK(x.dim() == 3 && x.size(2) == FIN && x.is_contiguous(),
+                "x must be a contiguous (B,Ee,4)");
     const LdsPlan plan = cheb_lds_plan(Ee, K, FWD_NBUF, true, max_nnz);
     TORCH_CHECK(plan.fits, "graph too large for fused ChebConv");
     auto acts = torch::empty({B, L + 1, Ee, F}, x.options());
     auto t1s = torch::empty({B, L, Ee, F}, x.options());
     auto lam = torch::empty({B, Ee}, x.options());
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(cheb_fwd_kernel, dim3(B), dim3(512), plan.lds_bytes,
-                       stream.stream(),
+    hipLaunchKernelGGL(edge ? cheb_fwd_kernel<true> : cheb_fwd_kernel<false>,
+                       dim3(B), dim3(512), plan.lds_bytes, stream.stream(),
                        x.data_ptr<float>(), W.data_ptr<float>(),
                        bias.data_ptr<float>(), ext_indptr.data_ptr<int>(),
                        ext_base.data_ptr<long>(), ext_cols.data_ptr<int>(),
@@ -601,6 +964,29 @@ std::vector<torch::Tensor> cheb_fwd_hip(
                        lam.data_ptr<float>(),
                        Ee, L, K, plan.rows_pad, plan.stage_csr);
     return {lam, acts, t1s};
+}
+
+std::vector<torch::Tensor> cheb_fwd_hip(
+    torch::Tensor x, torch::Tensor W, torch::Tensor bias,
+    torch::Tensor ext_indptr, torch::Tensor ext_base,
+    torch::Tensor ext_cols, long max_nnz) {
+    return cheb_fwd_launch(x, W, bias, ext_indptr, ext_base, ext_cols,
+                           max_nnz, false);
+}
+
+// The forward for weights whose real output width the caller states
+// (W, bias zero-padded outside the real shapes).  Width 1 and L >= 2 take
+// the edge-layer path, anything else the full-width one.  Returns (lam,
+// acts, t1s, edge); with edge set, acts slots 0 and L and the tail of t1s
+// slot 0 are unwritten and only cheb_bwd_edge(..., edge) reads the rest.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, bool>
+cheb_fwd_edge_hip(torch::Tensor x, torch::Tensor W, torch::Tensor bias,
+                  torch::Tensor ext_indptr, torch::Tensor ext_base,
+                  torch::Tensor ext_cols, long max_nnz, long out_width) {
+    const bool edge = !cheb_full_forced && out_width == 1 && W.size(0) >= 2;
+    auto out = cheb_fwd_launch(x, W, bias, ext_indptr, ext_base, ext_cols,
+                               max_nnz, edge);
+    return {out[0], out[1], out[2], edge};
 }
 
 std::vector<torch::Tensor> cheb_kn_fwd_hip(
@@ -651,27 +1037,62 @@ std::vector<torch::Tensor> cheb_kn_bwd_hip(
     return {dW, db};
 }
 
-std::vector<torch::Tensor> cheb_bwd_hip_mask(
-    torch::Tensor dlam, torch::Tensor acts, torch::Tensor t1s,
-    torch::Tensor W, torch::Tensor ext_indptr, torch::Tensor ext_base,
-    torch::Tensor ext_cols, long max_nnz, long stage_mask) {
+// edge: the forward's flag; x and lam are read only when it is set
+std::vector<torch::Tensor> cheb_bwd_edge_hip_mask(
+    torch::Tensor dlam, torch::Tensor x, torch::Tensor lam,
+    torch::Tensor acts, torch::Tensor t1s, torch::Tensor W,
+    torch::Tensor ext_indptr, torch::Tensor ext_base,
+    torch::Tensor ext_cols, long max_nnz, bool edge, long stage_mask) {
     const int B = dlam.size(0), Ee = dlam.size(1);
     const int L = W.size(0), K = W.size(1);
+    TORCH_CHECK(K <= 2, "fused ChebConv kernel supports K<=2");
+    TORCH_CHECK(dlam.is_contiguous() && acts.size(0) == B &&
+                acts.size(1) == L + 1 && acts.size(2) == Ee &&
+                t1s.size(0) == B && t1s.size(1) == L && t1s.size(2) == Ee,
+                "cheb_bwd: dlam / acts / t1s shapes disagree");
+    if (edge)
+        TORCH_CHECK(L >= 2 && x.dim() == 3 && x.size(0) == B &&
+                    x.size(1) == Ee && x.size(2) == FIN &&
+                    x.is_contiguous() && lam.dim() == 2 &&
+                    lam.size(0) == B && lam.size(1) == Ee &&
+                    lam.is_contiguous(),
+                    "cheb_bwd_edge: x (B,Ee,4) and lam (B,Ee) of the "
+                    "forward expected");
     const LdsPlan plan = cheb_lds_plan(Ee, K, BWD_NBUF, false, max_nnz);
     TORCH_CHECK(plan.fits, "graph too large for fused ChebConv bwd");
     auto dW = torch::zeros({B, L, K, F, F}, dlam.options());
     auto db = torch::zeros({B, L, F}, dlam.options());
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(cheb_bwd_kernel, dim3(B), dim3(512), plan.lds_bytes,
-                       stream.stream(),
-                       dlam.data_ptr<float>(), acts.data_ptr<float>(),
-                       t1s.data_ptr<float>(),
+    hipLaunchKernelGGL(edge ? cheb_bwd_kernel<true> : cheb_bwd_kernel<false>,
+                       dim3(B), dim3(512), plan.lds_bytes, stream.stream(),
+                       dlam.data_ptr<float>(),
+                       edge ? x.data_ptr<float>() : nullptr,
+                       edge ? lam.data_ptr<float>() : nullptr,
+                       acts.data_ptr<float>(), t1s.data_ptr<float>(),
                        W.data_ptr<float>(), ext_indptr.data_ptr<int>(),
                        ext_base.data_ptr<long>(), ext_cols.data_ptr<int>(),
                        dW.data_ptr<float>(), db.data_ptr<float>(),
                        Ee, L, K, plan.rows_pad, plan.stage_csr,
                        (int)stage_mask);
     return {dW, db};
+}
+
+std::vector<torch::Tensor> cheb_bwd_edge_hip(
+    torch::Tensor dlam, torch::Tensor x, torch::Tensor lam,
+    torch::Tensor acts, torch::Tensor t1s, torch::Tensor W,
+    torch::Tensor ext_indptr, torch::Tensor ext_base,
+    torch::Tensor ext_cols, long max_nnz, bool edge) {
+    return cheb_bwd_edge_hip_mask(dlam, x, lam, acts, t1s, W, ext_indptr,
+                                  ext_base, ext_cols, max_nnz, edge, 0xF);
+}
+
+std::vector<torch::Tensor> cheb_bwd_hip_mask(
+    torch::Tensor dlam, torch::Tensor acts, torch::Tensor t1s,
+    torch::Tensor W, torch::Tensor ext_indptr, torch::Tensor ext_base,
+    torch::Tensor ext_cols, long max_nnz, long stage_mask) {
+    return cheb_bwd_edge_hip_mask(dlam, torch::Tensor(), torch::Tensor(),
+                                  acts, t1s, W, ext_indptr, ext_base,
+                                  ext_cols, max_nnz, false, stage_mask);
 }
 
 std::vector<torch::Tensor> cheb_bwd_hip(

@@ -24,6 +24,14 @@ build without the staging switch it times the kernels as they are.
 ``--config apsp`` times the Floyd–Warshall launch of the step (``eng.apsp``)
 on the same batch and on the mixed 20–110 engine, register-resident kernel
 against the in-place LDS kernel (``fw_force_inplace``).
+
+``--config cheb`` times the K<=2 ChebConv kernels (cheb_fwd, cheb_bwd) on the
+same batch at B=256 and B=1024, on the edge-layer path and forced onto the
+full-width path (``cheb_force_full_width``), with the model's 5-layer weight
+stack and with a 3-layer one (first, one middle, last layer — the kernels
+take L from ``W``): (t5 - t3) / 2 is one middle layer, the rest of t5 the two
+edge layers and the launch.  On a build without the switch it times the
+kernels as they are.
 """
 import argparse
 import json
@@ -400,11 +408,67 @@ def bench_apsp(batches=(256, 1024), reps=200):
             print(json.dumps(row), flush=True)
 
 
+def bench_cheb(batches=(256, 1024), reps=200):
+    from multihop_offload_amd.engine import EpisodeEngine
+    from multihop_offload_amd.models.chebconv import ChebConvStack
+    from multihop_offload_amd.harness.train_batched import build_training_cases
+    from multihop_offload_amd.ops import dispatch
+    from multihop_offload_amd.ops.functions import pack_cheb_params
+
+    ext = dispatch.require_hip()
+    has_switch = hasattr(ext, "cheb_force_full_width")
+    modes = ["edge", "full"] if has_switch else ["as_built"]
+    for batch in batches:
+        cases = build_training_cases(100, batch, 16, 1000, 100, gtype="ba",
+                                     workers=8)
+        model = ChebConvStack(K=2, dtype=torch.float32, seed=3)
+        with torch.no_grad():
+            for p in model.parameters():
+                p.mul_(0.01)
+            model.layers[-1].bias.fill_(0.5)
+        eng = EpisodeEngine(cases, model, device="cuda", dtype=torch.float32)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(0)
+        jobs = eng.sample_jobs(0.15, gen)
+        x = eng._features(jobs).contiguous()
+        csr = (eng.k_ext_indptr, eng.k_ext_base, eng.k_ext_cols,
+               eng.k_ext_max_nnz)
+        layers = list(eng.model.layers)
+        for nl in (3, 5):
+            params = []
+            for layer in layers[:nl - 1] + layers[-1:]:
+                params += [layer.weight, layer.bias]
+            Wp, bp = pack_cheb_params(params)
+            row = {"config": "cheb", "B": eng.B, "Ee": eng.Ee, "L": nl}
+            for mode in modes:
+                if has_switch:
+                    ext.cheb_force_full_width(mode == "full")
+                    fwd = lambda: ext.cheb_fwd_edge(      # noqa: E731
+                        x, Wp, bp, *csr, 1)
+                    lam, acts, t1s, edge = fwd()
+                    assert edge == (mode == "edge")
+                    dlam = torch.randn_like(lam)
+                    bwd = lambda: ext.cheb_bwd_edge(      # noqa: E731
+                        dlam, x, lam, acts, t1s, Wp, *csr, edge)
+                else:
+                    fwd = lambda: ext.cheb_fwd(x, Wp, bp, *csr)  # noqa: E731
+                    lam, acts, t1s = fwd()
+                    dlam = torch.randn_like(lam)
+                    bwd = lambda: ext.cheb_bwd(           # noqa: E731
+                        dlam, acts, t1s, Wp, *csr)
+                row[f"cheb_fwd_{mode}_us"] = round(timeit(fwd, reps, 20), 1)
+                row[f"cheb_bwd_{mode}_us"] = round(timeit(bwd, reps, 20), 1)
+            if has_switch:
+                ext.cheb_force_full_width(False)
+            print(json.dumps(row), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="both",
                     choices=["flagship", "er1000", "both", "timeslot",
-                             "timeslot_stats", "fixedpoint", "apsp"])
+                             "timeslot_stats", "fixedpoint", "apsp",
+                             "cheb"])
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--budgets", type=str, default="-1",
                     help="fixedpoint: staging budgets in bytes, comma-"
@@ -416,6 +480,8 @@ if __name__ == "__main__":
                          reps=max(args.reps, 100))
     if args.config == "apsp":
         bench_apsp(reps=max(args.reps, 200))
+    if args.config == "cheb":
+        bench_cheb(reps=max(args.reps, 200))
     if args.config == "timeslot":
         bench_timeslot(reps=args.reps)
     if args.config == "timeslot_stats":
