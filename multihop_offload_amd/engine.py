@@ -174,6 +174,19 @@ class SimResult:
     trace: Optional[torch.Tensor] = None   # (B, T, 3) arrivals, departures,
     #                                        tasks in network per slot
     stats: Optional[SimStats] = None       # with simulate(stats=True)
+    sched_slots: Optional[torch.Tensor] = None   # (B, E) int32 slots t >=
+    #                  warmup a link was scheduled in, with simulate(mac="mwis")
+
+    def sched_share(self) -> torch.Tensor:
+        """(B, E) float64 share of a link's busy slots in which it was
+        scheduled (``mac="mwis"`` with ``stats=True``); nan where the link
+        was never busy."""
+        if self.sched_slots is None or self.stats is None:
+            raise ValueError("sched_share: needs simulate(stats=True, "
+                             "mac='mwis')")
+        E = self.sched_slots.shape[1]
+        return SimStats._ratio(self.sched_slots,
+                               self.stats.busy_slots[:, :E])
 
 
 class EpisodeEngine:
@@ -1177,7 +1190,7 @@ class EpisodeEngine:
     def simulate(self, jobs: JobBatch, result: EpisodeResult,
                  arrivals: torch.Tensor, warmup: int = 0,
                  trace: bool = False, stats: bool = False,
-                 late_after=None) -> SimResult:
+                 late_after=None, mac: str = "share") -> SimResult:
         """Replay an episode's decisions packet by packet: the per-timeslot
         simulator of ``sim.timeslot`` over ``result``'s routes, all B graphs
         in one HIP launch on the GPU.  ``arrivals`` is (B, T, J) counts
@@ -1188,7 +1201,16 @@ class EpisodeEngine:
         histograms, the age of the backlog and per-resource queue
         statistics; ``late_after`` (an int or a (B,) tensor) is the sojourn
         above which a task counts as late, by default ``floor(T)`` of each
-        graph, the analytic congestion horizon."""
+        graph, the analytic congestion horizon.  ``mac="mwis"`` replaces
+        the fluid sharing of a link's rate by a collision-free schedule (a
+        queue-weighted greedy independent set of the conflict graph per
+        slot, ``sim.timeslot.mwis_schedule``) and fills
+        ``SimResult.sched_slots``."""
+        if mac not in ops.MAC_MODES:
+            raise ValueError(f"simulate: mac must be one of {ops.MAC_MODES}, "
+                             f"not {mac!r}")
+        mwis = mac == "mwis"
+        sched = None
         if result.dst is None or result.route_links is None \
                 or result.nhop is None:
             raise ValueError("simulate: the EpisodeResult carries no routes")
@@ -1212,9 +1234,10 @@ class EpisodeEngine:
                 jobs.mask, jobs.ul, jobs.dl, self.link_rates, self.proc_bws,
                 self.k_conf_indptr, self.k_conf_base, self.k_conf_cols,
                 self.k_E_arr, self.k_N_arr, self.T_arr, warmup=warmup,
-                trace=trace, stats=stats, late_after=late_after)
+                trace=trace, stats=stats, late_after=late_after, mac=mac)
             delay_sum, count, tr = out[:3]
             st = out[3] if stats else None
+            sched = out[-1] if mwis else None
         else:
             from .sim.timeslot import num_delay_bins, simulate_routes
             if arrivals.numel() and (int(arrivals.max()) > 255
@@ -1229,6 +1252,8 @@ class EpisodeEngine:
             if stats:
                 st = ops.empty_stats(B, J, self.E + self.N,
                                      num_delay_bins(T_sim))
+            if mwis:
+                sched = torch.zeros(B, self.E, dtype=torch.int32)
             for b, g in enumerate(self.cases):
                 k = int(jobs.mask[b].sum())
                 assert bool(jobs.mask[b, :k].all()), "mask is a prefix"
@@ -1239,7 +1264,12 @@ class EpisodeEngine:
                     result.route_links[b, :k].cpu().numpy(),
                     result.nhop[b, :k].cpu().numpy(), arr_np[b][:, :k],
                     warmup=warmup, trace=trace, stats=stats,
-                    late_after=int(late_after[b]) if stats else None)
+                    late_after=int(late_after[b]) if stats else None,
+                    mac=mac)
+                if mwis:
+                    sched[b, :g.num_links] = torch.as_tensor(
+                        out[-1]["sched_slots"])
+                    out = out[:-1]
                 if stats:
                     ops.fill_stats(st, b, out[-1], slice(0, k),
                                    g.num_links, self.E)
@@ -1255,6 +1285,8 @@ class EpisodeEngine:
             tr = tr.to(self.device) if trace else None
             if stats:
                 st = {k: v.to(self.device) for k, v in st.items()}
+            if mwis:
+                sched = sched.to(self.device)
         cnt = count.to(torch.float64)
         mean = torch.where(count > 0,
                            delay_sum.to(torch.float64) / cnt.clamp(min=1),
@@ -1268,7 +1300,7 @@ class EpisodeEngine:
                           T_sim=int(T_sim), warmup=warmup)
         return SimResult(delay_sum=delay_sum, count=count, mean_delay=mean,
                          backlog=arrived - count.to(torch.int64), trace=tr,
-                         stats=st)
+                         stats=st, sched_slots=sched)
 
     def _collect_per_sample_grads(self):
         """Slice the per-graph dW/db partials stashed by ChebStackFn's

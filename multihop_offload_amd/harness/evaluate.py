@@ -26,7 +26,7 @@ from .train_batched import build_training_cases
 def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
              device, dtype, workers: int = 8, lam_margin: float = 0.0,
              refine: int = 0, simulate: int = 0, sim_warmup: int = 0,
-             sim_stats: bool = False):
+             sim_stats: bool = False, sim_mac: str = "share"):
     """Returns per-method aggregate {tau, congest_jobs, num_jobs} summed /
     averaged over all (size, case, instance).  ``simulate`` > 0 also replays
     every episode's routes in the per-timeslot packet simulator for that
@@ -44,14 +44,19 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
     with every task still in the network counted at its age so far: a lower
     bound that does not drop them) and ``sim_link_util_max`` /
     ``sim_node_util_max`` (the busiest link's and node's share of busy
-    slots)."""
+    slots).  ``sim_mac="mwis"`` computes every ``sim_*`` field under the
+    scheduled MAC of ``EpisodeEngine.simulate(mac="mwis")`` and, with
+    ``sim_stats``, adds ``sim_sched_share``: the scheduled slots of all
+    links over their busy slots."""
+    mwis = sim_mac == "mwis"
+
     def fresh():
         return {"tau_sum": 0.0, "tau_n": 0, "congest": 0, "jobs": 0,
                 "ratio_sum": 0.0, "ratio_n": 0, "sim_delay": 0,
                 "sim_tasks": 0, "sim_backlog": 0, "sim_arrived": 0,
                 "sim_hist": None, "sim_dmax": 0, "sim_late": 0,
                 "sim_stuck_age": 0, "sim_link_util": 0.0,
-                "sim_node_util": 0.0}
+                "sim_node_util": 0.0, "sim_sched": 0, "sim_busy": 0}
 
     def fields(d, jobs_too=False):
         out = {"tau": d["tau_sum"] / max(d["tau_n"], 1),
@@ -78,6 +83,9 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
                 if seen else float("nan"))
             out["sim_link_util_max"] = d["sim_link_util"]
             out["sim_node_util_max"] = d["sim_node_util"]
+            if mwis:
+                out["sim_sched_share"] = (d["sim_sched"] / d["sim_busy"]
+                                          if d["sim_busy"] else float("nan"))
         return out
 
     agg = {m: fresh() for m in ("baseline", "local", "GNN")}
@@ -108,7 +116,8 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
                 r = res.delay_emp / bl
                 ok = torch.isfinite(r)
                 sim = (engine.simulate(jobs, res, arrivals,
-                                       warmup=sim_warmup, stats=sim_stats)
+                                       warmup=sim_warmup, stats=sim_stats,
+                                       mac=sim_mac)
                        if simulate else None)
                 for d in (agg[m], ps[m]):
                     d["tau_sum"] += float(torch.nansum(res.tau))
@@ -140,6 +149,9 @@ def evaluate(model, sizes, cases_per_size, instances, T, load, seed,
                             float(util[:, :E].max()) if E else 0.0)
                         d["sim_node_util"] = max(d["sim_node_util"],
                                                  float(util[:, E:].max()))
+                        if mwis:
+                            d["sim_sched"] += int(sim.sched_slots.sum())
+                            d["sim_busy"] += int(st.busy_slots[:, :E].sum())
         engine.check_overflow()       # strict: truncated walks void an eval
         per_size[n] = {m: fields(d) for m, d in ps.items()}
     summary = {m: fields(d, jobs_too=True) for m, d in agg.items()}
@@ -179,10 +191,19 @@ def main(argv=None):
                     help="with --simulate: also report sim_p50 / sim_p95 / "
                          "sim_p99, sim_late_ratio, sim_tau_censored, "
                          "sim_link_util_max and sim_node_util_max")
+    ap.add_argument("--sim-mac", choices=("share", "mwis"), default="share",
+                    help="with --simulate: the MAC model of the replay. "
+                         "share: every busy link transmits at rate / (1 + "
+                         "busy conflicting links); mwis: a queue-weighted "
+                         "greedy independent set of the conflict graph "
+                         "transmits at full rate each slot (recorded as "
+                         "sim_mac; with --sim-stats also sim_sched_share)")
     ap.add_argument("--out", type=str, default="out/eval_summary.json")
     args = ap.parse_args(argv)
     if args.sim_stats and not args.simulate:
         ap.error("--sim-stats requires --simulate T_SIM")
+    if args.sim_mac != "share" and not args.simulate:
+        ap.error("--sim-mac requires --simulate T_SIM")
 
     device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
     dtype = torch.float32 if device.startswith("cuda") else torch.float64
@@ -202,11 +223,19 @@ def main(argv=None):
                                  refine=args.refine,
                                  simulate=args.simulate,
                                  sim_warmup=args.sim_warmup,
-                                 sim_stats=args.sim_stats)
+                                 sim_stats=args.sim_stats,
+                                 sim_mac=args.sim_mac)
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    # the default MAC leaves the file's key set as it was before --sim-mac
+    config = vars(args)
+    doc = {"summary": summary, "per_size": per_size, "config": config}
+    if args.sim_mac == "share":
+        config = {k: v for k, v in config.items() if k != "sim_mac"}
+        doc["config"] = config
+    else:
+        doc["sim_mac"] = args.sim_mac
     with open(args.out, "w") as f:
-        json.dump({"summary": summary, "per_size": per_size,
-                   "config": vars(args)}, f, indent=1)
+        json.dump(doc, f, indent=1)
     print(json.dumps(summary, indent=1))
     return summary
 

@@ -69,7 +69,8 @@ def fw_force_inplace(on: bool) -> None:
 
 def queue_csr_force_global(on: bool) -> None:
     """Make every later launch of the queueing kernels (critic, actor head,
-    walk_eval) read the conflict CSR from global memory instead of staging
+    walk_eval) and of the scheduled-MAC simulator (``timeslot_sim(mac=
+    "mwis")``) read the conflict CSR from global memory instead of staging
     it in LDS (``False`` restores the per-workgroup decision).  A host-side
     switch for before/after timings and the staged-vs-global tests; the
     results are bit-equal either way."""
@@ -134,10 +135,23 @@ def timeslot_stats_lds_plan(N: int, E: int, J: int) -> dict:
                                                        int(J)))
 
 
+def timeslot_mwis_lds_plan(N: int, E: int, J: int,
+                           stats: bool = False) -> dict:
+    """LDS plan of the simulator's scheduled-MAC launch
+    (``timeslot_sim(mac="mwis")``, with ``stats`` its statistics
+    counterpart): the regions of the plan it extends, then the schedule's
+    state, verdict and count words and the fp64 weights."""
+    return dict(_require_hip().timeslot_mwis_lds_plan(int(N), int(E), int(J),
+                                                      bool(stats)))
+
+
+MAC_MODES = ("share", "mwis")
+
+
 def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
                  proc_bws, conf_indptr, conf_base, conf_cols, E_arr, n_arr,
                  T_arr=None, warmup: int = 0, trace: bool = False,
-                 stats: bool = False, late_after=None):
+                 stats: bool = False, late_after=None, mac: str = "share"):
     """Batched per-timeslot packet simulation of ``sim.timeslot``.
 
     ``arrivals`` (B,T,J) integer counts (at most 255 each; masked job slots
@@ -155,7 +169,17 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
     per-resource ones (B,E+N) with link l at column l and node v at column
     E + v, E the batch-maximum link count; masked job slots and padded
     links and nodes are zero.  ``late_after`` is an int32 (B,) tensor or an
-    int (default ``T``: no sojourn is late)."""
+    int (default ``T``: no sojourn is late).
+
+    ``mac="mwis"`` runs the scheduled MAC of ``simulate_routes(mac="mwis")``
+    (a queue-weighted greedy independent set of the conflict graph serves
+    each slot at full rate) and appends ``sched_slots`` int32 (B,E) to the
+    returned tuple, zero on padded links.  Any other value but ``"share"``
+    raises ``ValueError``."""
+    if mac not in MAC_MODES:
+        raise ValueError(f"timeslot_sim: mac must be one of {MAC_MODES}, "
+                         f"not {mac!r}")
+    mwis = mac == "mwis"
     B, T, J = arrivals.shape
     if arrivals.numel() and (int(arrivals.max()) > 255
                              or int(arrivals.min()) < 0):
@@ -196,10 +220,11 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
             pool, bool(trace))
         if stats:
             from ..sim.timeslot import num_delay_bins
-            out = ext.timeslot_sim_stats(*args, late_after,
-                                         num_delay_bins(T))
+            fn = ext.timeslot_sim_mwis_stats if mwis \
+                else ext.timeslot_sim_stats
+            out = fn(*args, late_after, num_delay_bins(T))
         else:
-            out = ext.timeslot_sim(*args)
+            out = (ext.timeslot_sim_mwis if mwis else ext.timeslot_sim)(*args)
         delay_sum, count, error, tr = out[:4]
         if bool(error.any()):
             bad = torch.nonzero(error).flatten().tolist()
@@ -207,10 +232,12 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
                 "timeslot_sim: guard rail tripped (input out of range, pool "
                 f"or loop bound) in graphs {bad[:8]}, bits "
                 f"{error[bad[:8]].tolist()}")
+        ret = (delay_sum, count, (tr if trace else None))
         if stats:
-            return delay_sum, count, (tr if trace else None), \
-                dict(zip(STAT_KEYS, out[4:]))
-        return delay_sum, count, (tr if trace else None)
+            ret += (dict(zip(STAT_KEYS, out[4:4 + len(STAT_KEYS)])),)
+        if mwis:
+            ret += (out[-1],)
+        return ret
 
     from types import SimpleNamespace
 
@@ -225,6 +252,7 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
     N = proc_bws.shape[1]
     E = link_rates.shape[1]
     st = empty_stats(B, J, E + N, num_delay_bins(T)) if stats else None
+    sched = torch.zeros(B, E, dtype=torch.int32) if mwis else None
     for b in range(B):
         Eb = int(E_arr[b])
         lo = int(conf_base[b])
@@ -239,7 +267,11 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
             dl[b, idx].numpy().astype(np.float64), dst[b, idx].numpy(),
             route_links[b, idx].numpy(), nhop[b, idx].numpy(),
             arr[b][:, idx].numpy(), warmup=warmup, trace=trace,
-            stats=stats, late_after=int(late_after[b]) if stats else None)
+            stats=stats, late_after=int(late_after[b]) if stats else None,
+            mac=mac)
+        if mwis:
+            sched[b, :Eb] = torch.as_tensor(out[-1]["sched_slots"])
+            out = out[:-1]
         if stats:
             fill_stats(st, b, out[-1], idx, Eb, E)
         delay_sum[b, idx] = torch.as_tensor(out[0])
@@ -248,6 +280,9 @@ def timeslot_sim(arrivals, route_links, nhop, dst, mask, ul, dl, link_rates,
             for k, name in enumerate(("arrivals", "departures",
                                       "pkts_in_network")):
                 tr[b, :, k] = torch.as_tensor(out[2][name]).to(torch.int32)
+    ret = (delay_sum, count, tr)
     if stats:
-        return delay_sum, count, tr, st
-    return delay_sum, count, tr
+        ret += (st,)
+    if mwis:
+        ret += (sched,)
+    return ret

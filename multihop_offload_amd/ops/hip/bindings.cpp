@@ -72,6 +72,22 @@ std::vector<torch::Tensor> timeslot_sim_stats_hip(
     torch::Tensor n_arr, long warmup, long pool, bool want_trace,
     torch::Tensor late_after, long nbins);
 py::dict timeslot_stats_lds_plan(long N, long E, long J);
+std::vector<torch::Tensor> timeslot_sim_mwis_hip(
+    torch::Tensor arrivals, torch::Tensor slot_off, torch::Tensor route_links,
+    torch::Tensor nhop, torch::Tensor dst, torch::Tensor mask,
+    torch::Tensor ul, torch::Tensor dl, torch::Tensor conf_indptr,
+    torch::Tensor conf_base, torch::Tensor conf_cols, torch::Tensor rates,
+    torch::Tensor bw, torch::Tensor T_arr, torch::Tensor E_arr,
+    torch::Tensor n_arr, long warmup, long pool, bool want_trace);
+std::vector<torch::Tensor> timeslot_sim_mwis_stats_hip(
+    torch::Tensor arrivals, torch::Tensor slot_off, torch::Tensor route_links,
+    torch::Tensor nhop, torch::Tensor dst, torch::Tensor mask,
+    torch::Tensor ul, torch::Tensor dl, torch::Tensor conf_indptr,
+    torch::Tensor conf_base, torch::Tensor conf_cols, torch::Tensor rates,
+    torch::Tensor bw, torch::Tensor T_arr, torch::Tensor E_arr,
+    torch::Tensor n_arr, long warmup, long pool, bool want_trace,
+    torch::Tensor late_after, long nbins);
+py::dict timeslot_mwis_lds_plan(long N, long E, long J, bool stats);
 
 // step_glue.hip
 std::vector<torch::Tensor> cheb_pack_params_hip(
@@ -168,6 +184,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("timeslot_lds_plan", &timeslot_lds_plan);
     m.def("timeslot_sim_stats", &timeslot_sim_stats_hip);
     m.def("timeslot_stats_lds_plan", &timeslot_stats_lds_plan);
+    m.def("timeslot_sim_mwis", &timeslot_sim_mwis_hip);
+    m.def("timeslot_sim_mwis_stats", &timeslot_sim_mwis_stats_hip);
+    m.def("timeslot_mwis_lds_plan", &timeslot_mwis_lds_plan);
     m.def("cheb_fwd", &cheb_fwd_hip);
     m.def("cheb_bwd", &cheb_bwd_hip);
     m.def("cheb_bwd_ablate", &cheb_bwd_hip_mask);

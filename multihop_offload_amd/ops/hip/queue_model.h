@@ -537,17 +537,60 @@ inline TimeslotPlan timeslot_plan(int N, int E, int J) {
 struct TimeslotStatsPlan : TimeslotPlan {
     int qlen, qmax, bslots, qsum, nbsum;
 };
+inline void timeslot_stats_regions(TimeslotStatsPlan& p, Carve& c, int N,
+                                   int E, int J) {
+    const size_t R = (size_t)E + N;
+    timeslot_regions(p, c, N, E, J);
+    p.qlen = c.lds(R);
+    p.qmax = c.lds(R);
+    p.bslots = c.lds(R);
+    c.lds(c.floats & 1);                    // the 64-bit rows start even
+    p.qsum = c.lds(2 * R);
+    p.nbsum = c.lds(2 * (size_t)E);
+}
 inline TimeslotStatsPlan timeslot_stats_plan(int N, int E, int J) {
     return make_plan<TimeslotStatsPlan>(
         launch_threads(E, N), [=](TimeslotStatsPlan& p, Carve& c) {
-            const size_t R = (size_t)E + N;
+            timeslot_stats_regions(p, c, N, E, J);
+        });
+}
+
+// The scheduled-MAC launches (timeslot_sim_mwis, timeslot_sim_mwis_stats):
+// the regions of the plan above them in the same order, then the schedule's
+// own: the live queue length per resource where the plan has none yet, the
+// schedule state, the round's verdict and the scheduled-slot count (one word
+// per link), one pad word where the count so far is odd, and the 64-bit
+// weights.  With W the base plan's words and S the statistics plan's:
+//   4 * (W + R + 3 E + (W + R + 3 E) % 2 + 2 E) bytes, and
+//   4 * (S + 3 E + (S + 3 E) % 2 + 2 E) bytes with the statistics.
+struct MwisRegions { int sstate, swin, sslots, swt; };
+inline void timeslot_mwis_regions(MwisRegions& m, Carve& c, int E) {
+    m.sstate = c.lds(E);
+    m.swin = c.lds(E);
+    m.sslots = c.lds(E);
+    c.lds(c.floats & 1);                    // the 64-bit row starts even
+    m.swt = c.lds(2 * (size_t)E);
+}
+struct TimeslotMwisPlan : TimeslotPlan {
+    int qlen;
+    MwisRegions mw;
+};
+inline TimeslotMwisPlan timeslot_mwis_plan(int N, int E, int J) {
+    return make_plan<TimeslotMwisPlan>(
+        launch_threads(E, N), [=](TimeslotMwisPlan& p, Carve& c) {
             timeslot_regions(p, c, N, E, J);
-            p.qlen = c.lds(R);
-            p.qmax = c.lds(R);
-            p.bslots = c.lds(R);
-            c.lds(c.floats & 1);            // the 64-bit rows start even
-            p.qsum = c.lds(2 * R);
-            p.nbsum = c.lds(2 * (size_t)E);
+            p.qlen = c.lds((size_t)E + N);
+            timeslot_mwis_regions(p.mw, c, E);
+        });
+}
+struct TimeslotMwisStatsPlan : TimeslotStatsPlan {
+    MwisRegions mw;
+};
+inline TimeslotMwisStatsPlan timeslot_mwis_stats_plan(int N, int E, int J) {
+    return make_plan<TimeslotMwisStatsPlan>(
+        launch_threads(E, N), [=](TimeslotMwisStatsPlan& p, Carve& c) {
+            timeslot_stats_regions(p, c, N, E, J);
+            timeslot_mwis_regions(p.mw, c, E);
         });
 }
 

@@ -17,6 +17,18 @@
 // go to global memory beside delay_sum / count, and two more phases run after
 // the last slot.  Stats = false compiles to the statistics-free kernel.
 //
+// Scheduled MAC (timeslot_sim_mwis, timeslot_sim_mwis_stats) is the same text
+// again with Mwis = true: between the arrivals and the service of a slot the
+// workgroup runs the rounds of sim/timeslot.py::mwis_schedule over the
+// conflict rows (two barriers a round), and a scheduled link serves at its
+// full rate.  The weights are one fp64 multiply of an exactly converted queue
+// length and the widened fp32 rate, so every comparison agrees with the
+// oracle bit for bit.  Its plans (qm::timeslot_mwis_plan and its statistics
+// counterpart) append the schedule's words, and the launcher adds the staging
+// area of queue_model.h behind them where it fits (queue_csr_force_global and
+// queue_csr_set_budget apply); Mwis = false compiles to the two kernels
+// above, unchanged.
+//
 // A graph whose guard rails trip (tsim::ERR) stops stepping; error[b] carries
 // the bits and the Python wrapper raises.
 
@@ -40,13 +52,29 @@ struct StatArgs {                   // the statistics outputs, all prezeroed
     long long* nb_sum;
     int nbins;
 };
-template <bool Stats>
-using plan_t = std::conditional_t<Stats, qm::TimeslotStatsPlan,
-                                  qm::TimeslotPlan>;
+struct MwisArgs {
+    int* sched_slots;               // (B,E) prezeroed
+    int stage_budget;               // bytes of LDS after the plan's, or 0
+};
+template <bool Stats, bool Mwis = false>
+using plan_t = std::conditional_t<
+    Mwis,
+    std::conditional_t<Stats, qm::TimeslotMwisStatsPlan,
+                       qm::TimeslotMwisPlan>,
+    std::conditional_t<Stats, qm::TimeslotStatsPlan, qm::TimeslotPlan>>;
 
-// StatArg is the one StatArgs of the statistics launch and nothing at all
-// otherwise, so that Stats = false keeps the plain kernel's argument list.
-template <bool Stats, class... StatArg>
+// the one argument of type T among the mode arguments of a launch
+template <class T, class First, class... Rest>
+__device__ __forceinline__ const T& mode_arg(const First& first,
+                                             const Rest&... rest) {
+    if constexpr (std::is_same_v<T, First>) return first;
+    else return mode_arg<T>(rest...);
+}
+
+// ModeArg is the StatArgs of a statistics launch, then the MwisArgs of a
+// scheduled one, and nothing at all otherwise, so that the plain kernel
+// keeps its argument list.
+template <bool Stats, bool Mwis, class... ModeArg>
 __global__ void timeslot_kernel(
     const unsigned char* __restrict__ arrivals,   // (B,T,J)
     const int* __restrict__ slot_off,             // (B,T+1)
@@ -64,8 +92,8 @@ __global__ void timeslot_kernel(
     int* __restrict__ count,                      // (B,J) out
     int* __restrict__ error,                      // (B) out
     int* __restrict__ trace,                      // (B,T,3) prezeroed, or null
-    const plan_t<Stats> p, int N, int J, int H, int T, int warmup, int P,
-    const StatArg... stat_arg) {
+    const plan_t<Stats, Mwis> p, int N, int J, int H, int T, int warmup,
+    int P, const ModeArg... mode_args) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     int* w = reinterpret_cast<int*>(smem_raw);
 
@@ -105,7 +133,7 @@ __global__ void timeslot_kernel(
     st.count = count + (size_t)b * J;
     st.trace = trace ? trace + (size_t)b * T * 3 : nullptr;
     if constexpr (Stats) {
-        const StatArgs& sa = (stat_arg, ...);
+        const StatArgs& sa = mode_arg<StatArgs>(mode_args...);
         const size_t RS = (size_t)tb.E + N;     // per-resource output stride
         c.late_after = sa.late_after[b];
         c.nbins = sa.nbins;
@@ -124,6 +152,32 @@ __global__ void timeslot_kernel(
         st.busy_slots = sa.busy_slots + b * RS;
         st.nb_sum = sa.nb_sum + b * RS;
     }
+    if constexpr (Mwis) {
+        const MwisArgs& ma = mode_arg<MwisArgs>(mode_args...);
+        st.qlen = w + p.qlen;
+        st.sstate = w + p.mw.sstate;
+        st.swin = w + p.mw.swin;
+        st.sslots = w + p.mw.sslots;
+        st.swt = reinterpret_cast<double*>(w + p.mw.swt);
+        st.sched_slots = ma.sched_slots + (size_t)b * tb.E;
+    }
+    // The schedule walks the conflict rows up to two times a round: a graph
+    // whose columns fit the launch's staging area (after the plan's bytes,
+    // as for the fixed point's stage_csr) reads them from LDS as 16-bit
+    // words, any other graph from global memory.  Block-uniform.
+    unsigned short* c16 = nullptr;
+    if constexpr (Mwis) {
+        const MwisArgs& ma = mode_arg<MwisArgs>(mode_args...);
+        if (c.Eb >= 0 && c.Eb <= tb.E && c.Eb <= qm::STAGE_MAX_E) {
+            const int nnz = c.cip[c.Eb];
+            if (ma.stage_budget > 0 && nnz >= 0 &&
+                sizeof(unsigned short) * (size_t)nnz
+                    <= (size_t)ma.stage_budget)
+                c16 = reinterpret_cast<unsigned short*>(
+                    smem_raw + qm::stage_align(p.lds_bytes));
+        }
+        c.ccols16 = c16;
+    }
 
     // the ragged link count must fit the carve before anything indexes by it
     const bool sized = c.Eb >= 0 && c.Eb <= tb.E;
@@ -137,18 +191,41 @@ __global__ void timeslot_kernel(
     }
     tsim::init_jobs(c, st, tid, nt);
     __syncthreads();
-    tsim::init_queues<Stats>(c, st, tid, nt);
+    tsim::init_queues<Stats, Mwis>(c, st, tid, nt);
+    if constexpr (Mwis)
+        if (c16) tsim::stage_cols(c, st, c16, tid, nt);
     // The error word is only ever read through the barrier itself: a thread
     // that sets it reads its own store on arrival, so every thread gets the
     // same answer and the workgroup leaves the loop together.
     int err = __syncthreads_or(st.misc[tsim::ERR]);
     for (int t = 0; t < T && !err; ++t) {
-        tsim::arrive<Stats>(c, st, t, tid, nt);
+        tsim::arrive<Stats, Mwis>(c, st, t, tid, nt);
+        if constexpr (Mwis) {
+            // sched_init reads only what this thread's arrive wrote; the
+            // barrier that publishes the arrivals carries its answer.  Like
+            // err, `left` is the barrier's own result, so the workgroup
+            // leaves the round loop together.
+            int left = __syncthreads_or(tsim::sched_init(c, st, tid, nt));
+            for (int round = 0; left; ++round) {
+                if (round >= c.Eb) {            // cannot happen: see KERNELS.md
+                    if (tid == 0) st.misc[tsim::ERR] = tsim::E_BOUND;
+                    break;
+                }
+                tsim::sched_round_pick(c, st, tid, nt);
+                __syncthreads();
+                left = __syncthreads_or(
+                    tsim::sched_round_commit(c, st, tid, nt));
+            }
+        } else {
+            __syncthreads();
+        }
+        tsim::serve<Stats, Mwis>(c, st, t, tid, nt);
         __syncthreads();
-        tsim::serve<Stats>(c, st, t, tid, nt);
-        __syncthreads();
-        tsim::handover<Stats>(c, st, t, tid, nt);
+        tsim::handover<Stats, Mwis>(c, st, t, tid, nt);
         err = __syncthreads_or(st.misc[tsim::ERR]);
+    }
+    if constexpr (Mwis) {
+        if (!err) tsim::store_sched_slots(c, st, tid, nt);
     }
     if constexpr (Stats) {
         if (!err) {
@@ -160,9 +237,10 @@ __global__ void timeslot_kernel(
     if (tid == 0) error[b] = st.misc[tsim::ERR];
 }
 
-// Both entry points: checks, allocations and the launch of one instantiation.
-// Stats appends the nine statistic tensors to the four of the plain launch.
-template <bool Stats>
+// Every entry point: checks, allocations and the launch of one instantiation.
+// Stats appends the nine statistic tensors to the four of the plain launch,
+// Mwis appends sched_slots after them.
+template <bool Stats, bool Mwis = false>
 std::vector<torch::Tensor> timeslot_launch(
     torch::Tensor arrivals, torch::Tensor slot_off, torch::Tensor route_links,
     torch::Tensor nhop, torch::Tensor dst, torch::Tensor mask,
@@ -200,13 +278,21 @@ std::vector<torch::Tensor> timeslot_launch(
                 E_arr.numel() == B && n_arr.numel() == B &&
                 conf_base.numel() >= B, "batch tables disagree on B or E");
     TORCH_CHECK(pool >= 0 && warmup >= 0, "pool, warmup: non-negative");
-    plan_t<Stats> p;
+    plan_t<Stats, Mwis> p;
     if constexpr (Stats) {
         TORCH_CHECK(late_after.is_cuda() && late_after.is_contiguous() &&
                     late_after.scalar_type() == torch::kInt32 &&
                     late_after.numel() == B, "late_after: int32 (B)");
         TORCH_CHECK(nbins >= 1 && nbins <= T + 1,
                     "nbins: sim.timeslot.num_delay_bins(T)");
+    }
+    if constexpr (Stats && Mwis) {
+        p = qm::timeslot_mwis_stats_plan(N, E, J);
+        TORCH_CHECK(p.fits, "graph too large for LDS timeslot_sim_mwis_stats");
+    } else if constexpr (Mwis) {
+        p = qm::timeslot_mwis_plan(N, E, J);
+        TORCH_CHECK(p.fits, "graph too large for LDS timeslot_sim_mwis");
+    } else if constexpr (Stats) {
         p = qm::timeslot_stats_plan(N, E, J);
         TORCH_CHECK(p.fits, "graph too large for LDS timeslot_sim_stats");
     } else {
@@ -251,10 +337,18 @@ std::vector<torch::Tensor> timeslot_launch(
         stat_out = {delay_max, late, delay_hist, stuck, stuck_age,
                     qlen_sum, qlen_max, busy_slots, nb_sum};
     }
+    MwisArgs ma{};
+    torch::Tensor sched_slots;
+    if constexpr (Mwis) {
+        sched_slots = torch::zeros({B, E}, opts_i);
+        ma.sched_slots = sched_slots.data_ptr<int>();
+        ma.stage_budget = qm::stage_budget(p);
+    }
+    const size_t lds_bytes = qm::launch_lds_bytes(p, ma.stage_budget);
     auto stream = at::cuda::getCurrentCUDAStream();
-    auto launch = [&](auto kernel, auto... stat_arg) {
+    auto launch = [&](auto kernel, auto... mode_args) {
         hipLaunchKernelGGL(
-            kernel, dim3(B), dim3(p.threads), p.lds_bytes, stream.stream(),
+            kernel, dim3(B), dim3(p.threads), lds_bytes, stream.stream(),
             arrivals.data_ptr<uint8_t>(), slot_off.data_ptr<int>(),
             route_links.data_ptr<int>(), nhop.data_ptr<int>(),
             dst.data_ptr<long>(), mask.data_ptr<bool>(),
@@ -266,13 +360,20 @@ std::vector<torch::Tensor> timeslot_launch(
             reinterpret_cast<long long*>(delay_sum.data_ptr<long>()),
             count.data_ptr<int>(), error.data_ptr<int>(),
             want_trace ? trace.data_ptr<int>() : nullptr, p, N, J, H, T,
-            (int)warmup, (int)P, stat_arg...);
+            (int)warmup, (int)P, mode_args...);
     };
-    if constexpr (Stats) launch(timeslot_kernel<true, StatArgs>, sa);
-    else launch(timeslot_kernel<false>);
+    if constexpr (Stats && Mwis)
+        launch(timeslot_kernel<true, true, StatArgs, MwisArgs>, sa, ma);
+    else if constexpr (Mwis)
+        launch(timeslot_kernel<false, true, MwisArgs>, ma);
+    else if constexpr (Stats)
+        launch(timeslot_kernel<true, false, StatArgs>, sa);
+    else
+        launch(timeslot_kernel<false, false>);
     if (!want_trace) trace = torch::empty({0}, opts_i);
     std::vector<torch::Tensor> out = {delay_sum, count, error, trace};
     out.insert(out.end(), stat_out.begin(), stat_out.end());
+    if constexpr (Mwis) out.push_back(sched_slots);
     return out;
 }
 
@@ -310,6 +411,36 @@ std::vector<torch::Tensor> timeslot_sim_stats_hip(
         want_trace, late_after, nbins);
 }
 
+// The scheduled MAC of sim/timeslot.py (mac="mwis"): what timeslot_sim
+// returns, then sched_slots int32 (B,E), zero on padded links.
+std::vector<torch::Tensor> timeslot_sim_mwis_hip(
+    torch::Tensor arrivals, torch::Tensor slot_off, torch::Tensor route_links,
+    torch::Tensor nhop, torch::Tensor dst, torch::Tensor mask,
+    torch::Tensor ul, torch::Tensor dl, torch::Tensor conf_indptr,
+    torch::Tensor conf_base, torch::Tensor conf_cols, torch::Tensor rates,
+    torch::Tensor bw, torch::Tensor T_arr, torch::Tensor E_arr,
+    torch::Tensor n_arr, long warmup, long pool, bool want_trace) {
+    return timeslot_launch<false, true>(
+        arrivals, slot_off, route_links, nhop, dst, mask, ul, dl, conf_indptr,
+        conf_base, conf_cols, rates, bw, T_arr, E_arr, n_arr, warmup, pool,
+        want_trace, torch::Tensor(), 0);
+}
+
+// ... with the statistics: what timeslot_sim_stats returns, then sched_slots.
+std::vector<torch::Tensor> timeslot_sim_mwis_stats_hip(
+    torch::Tensor arrivals, torch::Tensor slot_off, torch::Tensor route_links,
+    torch::Tensor nhop, torch::Tensor dst, torch::Tensor mask,
+    torch::Tensor ul, torch::Tensor dl, torch::Tensor conf_indptr,
+    torch::Tensor conf_base, torch::Tensor conf_cols, torch::Tensor rates,
+    torch::Tensor bw, torch::Tensor T_arr, torch::Tensor E_arr,
+    torch::Tensor n_arr, long warmup, long pool, bool want_trace,
+    torch::Tensor late_after, long nbins) {
+    return timeslot_launch<true, true>(
+        arrivals, slot_off, route_links, nhop, dst, mask, ul, dl, conf_indptr,
+        conf_base, conf_cols, rates, bw, T_arr, E_arr, n_arr, warmup, pool,
+        want_trace, late_after, nbins);
+}
+
 py::dict timeslot_lds_plan(long N, long E, long J) {
     using namespace pybind11::literals;
     const qm::TimeslotPlan p = qm::timeslot_plan((int)N, (int)E, (int)J);
@@ -321,6 +452,17 @@ py::dict timeslot_stats_lds_plan(long N, long E, long J) {
     using namespace pybind11::literals;
     const qm::TimeslotStatsPlan p =
         qm::timeslot_stats_plan((int)N, (int)E, (int)J);
+    return py::dict("lds_bytes"_a = p.lds_bytes, "large"_a = p.large,
+                    "threads"_a = p.threads, "fits"_a = p.fits);
+}
+
+py::dict timeslot_mwis_lds_plan(long N, long E, long J, bool stats) {
+    using namespace pybind11::literals;
+    const qm::Launch p = stats
+        ? static_cast<qm::Launch>(
+              qm::timeslot_mwis_stats_plan((int)N, (int)E, (int)J))
+        : static_cast<qm::Launch>(
+              qm::timeslot_mwis_plan((int)N, (int)E, (int)J));
     return py::dict("lds_bytes"_a = p.lds_bytes, "large"_a = p.large,
                     "threads"_a = p.threads, "fits"_a = p.fits);
 }

@@ -28,6 +28,24 @@
 // two phases follow the last slot: tally_backlog and store_resource_stats.
 // All of it is integers, each word with one writer or an integer sum.
 //
+// Scheduled MAC: a second template parameter `Mwis`, false by default, swaps
+// the link capacity rate / (1 + nb) for the slot's schedule
+// (sim/timeslot.py::mwis_schedule): the owner of r keeps qlen[r] (as with
+// Stats), and between arrive and serve the caller runs
+//   sched_init        : weight qlen * rate (one fp64 multiply) and the
+//                       candidate flag of every link
+//   then per round, while sched_init / sched_round_commit report a candidate:
+//   sched_round_pick  : the owner of a candidate scans its conflict row and
+//                       writes its own verdict (won / lost)
+//   sched_round_commit: a winner marks itself scheduled and its neighbours
+//                       out — the one shared write, every writer storing the
+//                       same value
+// serve<Stats, true> gives a scheduled link its full rate and any other link
+// nothing, and counts the scheduled slots t >= warmup; store_sched_slots
+// follows the last slot.  These phases read the conflict columns through
+// conf_col: the 16-bit copy that stage_cols made at init, where the caller
+// had room for one, and ccols in place otherwise.
+//
 // Guard rails: every index read from memory is range-checked before use and
 // every loop has a bound derived from the pool capacity P; a violation sets
 // st.misc[ERR] and the caller stops stepping that graph.
@@ -79,6 +97,9 @@ struct Case {                       // one graph, read-only
     int late_after = 0;             // sojourns above it count as late
     int nbins = 0;                  // delay_bin(T) + 1 histogram bins
     int node_col = 0;               // output column of node 0 (batch max E)
+    // scheduled MAC only: ccols as 16-bit words (LDS on the GPU, filled by
+    // stage_cols), or null: read ccols in place
+    const unsigned short* ccols16 = nullptr;
 };
 
 struct State {                      // one graph, mutable
@@ -126,9 +147,27 @@ struct State {                      // one graph, mutable
     int* qlen_max = nullptr;
     int* busy_slots = nullptr;
     long long* nb_sum = nullptr;
+    // scheduled MAC only (LDS on the GPU); qlen above is live here too
+    double* swt = nullptr;          // (Eb) the slot's weights
+    int* sstate = nullptr;          // (Eb) S_OUT / S_CAND / S_ON
+    int* swin = nullptr;            // (Eb) the round's verdict, W_*
+    int* sslots = nullptr;          // (Eb) scheduled slots t >= warmup
+    int* sched_slots = nullptr;     // output, zeroed by the caller
 };
 
+enum { S_OUT = 0, S_CAND = 1, S_ON = 2 };       // a link in the slot's schedule
+enum { W_NONE = 0, W_WON = 1, W_LOST = 2 };     // a candidate's round
+
 DEV_INLINE int num_res(const Case& c) { return c.Eb + c.N; }
+
+// conflict column a of the graph: the scheduled MAC walks the rows several
+// times a slot and reads the staged copy where there is one
+template <bool Mwis>
+DEV_INLINE int conf_col(const Case& c, int a) {
+    if constexpr (Mwis)
+        if (c.ccols16) return (int)c.ccols16[a];
+    return c.ccols[a];
+}
 DEV_INLINE int mask_words(int R) { return (R + 31) / 32; }
 
 // Histogram bin of a sojourn d >= 0: exact below 16, then eight sub-bins per
@@ -204,7 +243,7 @@ DEV_INLINE void init_jobs(const Case& c, State& st, int tid, int nt) {
 }
 
 // ---- init, part 2: empty queues, per-resource job chains, slot 0 staged --
-template <bool Stats = false>
+template <bool Stats = false, bool Mwis = false>
 DEV_INLINE void init_queues(const Case& c, State& st, int tid, int nt) {
     const int R = num_res(c);
     for (int r = tid; r < R; r += nt) {
@@ -216,6 +255,15 @@ DEV_INLINE void init_queues(const Case& c, State& st, int tid, int nt) {
             st.qsum[r] = 0;
             if (r < c.Eb) st.nbsum[r] = 0;
         }
+        if constexpr (Mwis) {
+            st.qlen[r] = 0;
+            if (r < c.Eb) {
+                st.swt[r] = 0.0;
+                st.sstate[r] = S_OUT;
+                st.swin[r] = W_NONE;
+                st.sslots[r] = 0;
+            }
+        }
         int first = -1;
         for (int j = c.J - 1; j >= 0; --j)
             if (st.jres[j] == r) { st.jnext[j] = first; first = j; }
@@ -226,8 +274,23 @@ DEV_INLINE void init_queues(const Case& c, State& st, int tid, int nt) {
     if (c.T > 0) stage_arrivals(c, st, 0, tid, nt);
 }
 
+// ---- scheduled MAC, init: the conflict columns staged as 16-bit words ------
+// `c16` holds cip[Eb] words and is what c.ccols16 points to; the caller has
+// checked Eb <= 65535.  A column that the narrowing would alias onto a valid
+// link is reported here, since the range checks of the phases can no longer
+// see it.  Runs with init_queues (after init_jobs has written misc[ERR]).
+DEV_INLINE void stage_cols(const Case& c, State& st, unsigned short* c16,
+                           int tid, int nt) {
+    const int nnz = c.cip[c.Eb];
+    for (int a = tid; a < nnz; a += nt) {
+        const int o = c.ccols[a];
+        if (o < 0 || o >= c.Eb) st.misc[ERR] = E_INPUT;
+        c16[a] = (unsigned short)o;
+    }
+}
+
 // ---- arrivals of slot t, then the busy snapshot ---------------------------
-template <bool Stats = false>
+template <bool Stats = false, bool Mwis = false>
 DEV_INLINE void arrive(const Case& c, State& st, int t, int tid, int nt) {
     const int R = num_res(c);
     for (int w = tid; w < mask_words(R); w += nt) st.fmask[w] = 0u;
@@ -250,23 +313,88 @@ DEV_INLINE void arrive(const Case& c, State& st, int t, int tid, int nt) {
                 st.rem[q] = units;
                 append(st, r, q);
             }
-            if constexpr (Stats) added += k;
+            if constexpr (Stats || Mwis) added += k;
         }
         if (r < c.Eb) st.busy[r] = st.head[r] >= 0;
-        if constexpr (Stats) {          // the sample: arrivals in, none served
-            const int len = st.qlen[r] + added;
+        if constexpr (Stats || Mwis) {
+            [[maybe_unused]] const int len = st.qlen[r] + added;
             if (added) st.qlen[r] = len;
-            if (t >= c.warmup && len > 0) {
-                st.qsum[r] += len;
-                if (len > st.qmax[r]) st.qmax[r] = len;
-                st.bslots[r] += 1;
+            if constexpr (Stats) {      // the sample: arrivals in, none served
+                if (t >= c.warmup && len > 0) {
+                    st.qsum[r] += len;
+                    if (len > st.qmax[r]) st.qmax[r] = len;
+                    st.bslots[r] += 1;
+                }
             }
         }
     }
 }
 
+// ---- scheduled MAC: the slot's weights and candidates ----------------------
+// After arrive: qlen is the FIFO length the oracle weighs, and every word
+// here belongs to the thread that wrote it there.  Returns whether this
+// thread owns a candidate: the first round's go-ahead.
+DEV_INLINE bool sched_init(const Case& c, State& st, int tid, int nt) {
+    bool any = false;
+    for (int l = tid; l < c.Eb; l += nt) {
+        const double w = (double)st.qlen[l] * (double)c.rates[l];
+        st.swt[l] = w;
+        st.sstate[l] = w > 0.0 ? S_CAND : S_OUT;
+        st.swin[l] = W_NONE;
+        any = any || w > 0.0;
+    }
+    return any;
+}
+
+// One round, part 1: a candidate wins when (w, -id) beats every candidate of
+// its conflict row.  Only swin[l] is written, by l's owner.
+DEV_INLINE void sched_round_pick(const Case& c, State& st, int tid, int nt) {
+    for (int l = tid; l < c.Eb; l += nt) {
+        int verdict = W_NONE;
+        if (st.sstate[l] == S_CAND) {
+            const double w = st.swt[l];
+            verdict = W_WON;
+            for (int a = c.cip[l]; a < c.cip[l + 1]; ++a) {
+                const int o = conf_col<true>(c, a);
+                if (o < 0 || o >= c.Eb) { st.misc[ERR] = E_INPUT; break; }
+                if (st.sstate[o] != S_CAND) continue;
+                const double wo = st.swt[o];
+                if (!(w > wo || (w == wo && l < o))) {
+                    verdict = W_LOST;
+                    break;
+                }
+            }
+        }
+        st.swin[l] = verdict;
+    }
+}
+
+// One round, part 2: winners join the schedule and put their neighbours out.
+// Two winners may both store S_OUT to a shared neighbour; a neighbour that
+// won itself (possible only with asymmetric rows) keeps its own S_ON.
+// Returns whether a candidate of this thread lost the round: the caller goes
+// on while any thread says so.  That is read off the verdicts alone, so a
+// loser that a winner has just put out still asks for one more round, which
+// then finds no candidate.
+DEV_INLINE bool sched_round_commit(const Case& c, State& st, int tid,
+                                   int nt) {
+    bool left = false;
+    for (int l = tid; l < c.Eb; l += nt) {
+        const int verdict = st.swin[l];
+        left = left || verdict == W_LOST;
+        if (verdict != W_WON) continue;
+        st.sstate[l] = S_ON;
+        for (int a = c.cip[l]; a < c.cip[l + 1]; ++a) {
+            const int o = conf_col<true>(c, a);
+            if (o < 0 || o >= c.Eb) { st.misc[ERR] = E_INPUT; break; }
+            if (st.swin[o] != W_WON) st.sstate[o] = S_OUT;
+        }
+    }
+    return left;
+}
+
 // ---- service: every resource drains its own FIFO --------------------------
-template <bool Stats = false>
+template <bool Stats = false, bool Mwis = false>
 DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
     const int R = num_res(c);
     for (int r = tid; r < R; r += nt) {
@@ -277,14 +405,25 @@ DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
             double cap;
             if (r < c.Eb) {
                 int nb = 0;
-                for (int a = c.cip[r]; a < c.cip[r + 1]; ++a) {
-                    const int o = c.ccols[a];
-                    if (o < 0 || o >= c.Eb) { st.misc[ERR] = E_INPUT; break; }
-                    nb += st.busy[o];
+                if constexpr (Stats || !Mwis) {
+                    for (int a = c.cip[r]; a < c.cip[r + 1]; ++a) {
+                        const int o = conf_col<Mwis>(c, a);
+                        if (o < 0 || o >= c.Eb) {
+                            st.misc[ERR] = E_INPUT;
+                            break;
+                        }
+                        nb += st.busy[o];
+                    }
                 }
                 if constexpr (Stats)
                     if (t >= c.warmup) st.nbsum[r] += nb;
-                cap = (double)c.rates[r] / (1.0 + (double)nb);
+                if constexpr (Mwis) {       // the schedule: all or nothing
+                    const bool on = st.sstate[r] == S_ON;
+                    if (on && t >= c.warmup) st.sslots[r] += 1;
+                    cap = on ? (double)c.rates[r] : 0.0;
+                } else {
+                    cap = (double)c.rates[r] / (1.0 + (double)nb);
+                }
             } else {
                 cap = (double)c.bw[r - c.Eb];
             }
@@ -302,7 +441,7 @@ DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
                 if (j < 0 || j >= c.J) { st.misc[ERR] = E_POOL; break; }
                 const int stage = st.stage[q] + 1;
                 st.stage[q] = stage;
-                if constexpr (Stats) ++popped;
+                if constexpr (Stats || Mwis) ++popped;
                 const int nr = leg_res(c, st, j, stage);
                 if (nr < 0) {                       // no legs left
                     const int t0 = st.t0[q];
@@ -337,7 +476,7 @@ DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
             }
             st.head[r] = q;
             if (q < 0) st.tail[r] = -1;
-            if constexpr (Stats)
+            if constexpr (Stats || Mwis)
                 if (popped) st.qlen[r] -= popped;
         }
         st.fhead[r] = fh;
@@ -348,7 +487,7 @@ DEV_INLINE void serve(const Case& c, State& st, int t, int tid, int nt) {
 }
 
 // ---- hand-over: finished tasks join their next queue, oracle order --------
-template <bool Stats = false>
+template <bool Stats = false, bool Mwis = false>
 DEV_INLINE void handover(const Case& c, State& st, int t, int tid, int nt) {
     const int R = num_res(c);
     for (int r = tid; r < R; r += nt) {
@@ -373,7 +512,7 @@ DEV_INLINE void handover(const Case& c, State& st, int t, int tid, int nt) {
                     }
                     if (tg == r) {
                         append(st, r, q);
-                        if constexpr (Stats) ++added;
+                        if constexpr (Stats || Mwis) ++added;
                     }
                     if (i + 1 < n) {
                         q = st.fnext[q];
@@ -385,7 +524,7 @@ DEV_INLINE void handover(const Case& c, State& st, int t, int tid, int nt) {
                 }
             }
         }
-        if constexpr (Stats)
+        if constexpr (Stats || Mwis)
             if (added) st.qlen[r] += added;
     }
     if (tid == 0) {
@@ -439,6 +578,11 @@ DEV_INLINE void store_resource_stats(const Case& c, State& st, int tid,
         st.busy_slots[col] = st.bslots[r];
         if (r < c.Eb) st.nb_sum[col] = st.nbsum[r];
     }
+}
+
+// ---- scheduled MAC: the scheduled-slot counts leave for their columns ------
+DEV_INLINE void store_sched_slots(const Case& c, State& st, int tid, int nt) {
+    for (int l = tid; l < c.Eb; l += nt) st.sched_slots[l] = st.sslots[l];
 }
 
 }  // namespace tsim

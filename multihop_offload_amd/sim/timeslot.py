@@ -77,10 +77,50 @@ def num_delay_bins(T: int) -> int:
 STAT_KEYS = ("delay_max", "late", "delay_hist", "stuck", "stuck_age",
              "qlen_sum", "qlen_max", "busy_slots", "nb_sum")
 
+MAC_MODES = ("share", "mwis")
+
+
+def mwis_schedule(conf_indptr, conf_indices, weights):
+    """Distributed greedy maximum-weight independent set of the conflict
+    graph (``utils.mwis.local_greedy_search`` on CSR rows) — the schedule of
+    one slot under ``mac="mwis"``.
+
+    The candidates are the links with ``weights[l] > 0``.  In each round a
+    remaining candidate ``l`` wins when ``(w[l], -l) > (w[m], -m)`` for
+    every remaining candidate ``m`` of its conflict row: a strictly larger
+    weight, or an equal weight and the lower id.  All winners of a round are
+    scheduled; they and their neighbours leave the candidate set.  The rows
+    are symmetric without a self entry, so two adjacent links never win
+    together and every round has a winner.  Returns ``(on bool (E,),
+    rounds)``; ``rounds`` is 0 when there was no candidate."""
+    w = np.asarray(weights, dtype=np.float64)
+    E = len(w)
+    cip = np.asarray(conf_indptr)
+    cols = np.asarray(conf_indices)
+    cand = w > 0
+    on = np.zeros(E, dtype=bool)
+    rounds = 0
+    while cand.any():
+        rounds += 1
+        winners = []
+        for l in np.nonzero(cand)[0]:
+            for m in cols[cip[l]:cip[l + 1]]:
+                if cand[m] and not (w[l] > w[m] or (w[l] == w[m] and l < m)):
+                    break
+            else:
+                winners.append(int(l))
+        assert winners, "conflict rows are not symmetric"
+        for l in winners:
+            on[l] = True
+            cand[l] = False
+            cand[cols[cip[l]:cip[l + 1]]] = False
+    return on, rounds
+
 
 def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
                     warmup: int = 0, trace: bool = False,
-                    stats: bool = False, late_after=None):
+                    stats: bool = False, late_after=None,
+                    mac: str = "share"):
     """The simulator loop over explicit routes — the contract of the batched
     HIP kernel (ops/hip/timeslot.hip), which reproduces it integer for
     integer.
@@ -102,7 +142,21 @@ def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
     ``t >= warmup`` sampled after the slot's arrivals and before service:
     ``qlen_sum`` int64, ``qlen_max`` int32, ``busy_slots`` int32 (FIFO not
     empty) and, links only, ``nb_sum`` int64: the busy conflicting links
-    summed over the link's own busy slots."""
+    summed over the link's own busy slots.
+
+    ``mac="mwis"`` replaces the fluid sharing by a collision-free schedule:
+    after the slot's arrivals, ``w[l] = len(link_q[l]) * link_rates[l]`` (one
+    fp64 multiply), ``on, r = mwis_schedule(conf_indptr, conf_indices, w)``,
+    and only the links with ``on[l]`` serve, at the full ``link_rates[l]``.
+    Nodes, the hand-over order, the trace, the warmup and every statistic
+    keep their definitions (``busy_slots``: FIFO not empty; ``nb_sum``: busy
+    conflicting links).  The returned tuple then ends with one more element,
+    ``{"sched_slots": int32 (E,), "rounds_max": int}``: the slots ``t >=
+    warmup`` in which each link was scheduled, and the largest number of
+    rounds any slot's schedule took."""
+    if mac not in MAC_MODES:
+        raise ValueError(f"mac: one of {MAC_MODES}, not {mac!r}")
+    mwis = mac == "mwis"
     arrivals = np.asarray(arrivals)
     T, J = arrivals.shape
     E, N = int(g.num_links), int(g.num_nodes)
@@ -140,6 +194,9 @@ def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
         qlen_max = np.zeros(E + N, dtype=np.int32)
         busy_slots = np.zeros(E + N, dtype=np.int32)
         nb_sum = np.zeros(E + N, dtype=np.int64)
+    if mwis:
+        sched_slots = np.zeros(E, dtype=np.int32)
+        rounds_max = 0
 
     def enqueue(task: _Task, t: int):
         while task.stage < len(legs[task.job]):
@@ -180,11 +237,23 @@ def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
                     busy_slots[r] += 1
                     if r < E:
                         nb_sum[r] += int(nb_busy[r])
+        if mwis:
+            w = np.array([np.float64(len(q)) * np.float64(link_rates[l])
+                          for l, q in enumerate(link_q)], dtype=np.float64)
+            on, r = mwis_schedule(conf_indptr, conf_indices, w)
+            rounds_max = max(rounds_max, r)
+            if t >= warmup:
+                sched_slots += on
         finished = []
         for l in range(E):
             if not link_q[l]:
                 continue
-            cap = link_rates[l] / (1.0 + nb_busy[l])
+            if mwis:
+                if not on[l]:
+                    continue
+                cap = link_rates[l]
+            else:
+                cap = link_rates[l] / (1.0 + nb_busy[l])
             while cap > 0 and link_q[l]:
                 head = link_q[l][0]
                 served = min(cap, head.remaining)
@@ -235,18 +304,21 @@ def simulate_routes(g, ul, dl, dst, route_links, nhop, arrivals,
                  "stuck_age": stuck_age, "qlen_sum": qlen_sum,
                  "qlen_max": qlen_max, "busy_slots": busy_slots,
                  "nb_sum": nb_sum},)
+    if mwis:
+        out += ({"sched_slots": sched_slots, "rounds_max": int(rounds_max)},)
     return out
 
 
 def simulate(g: CaseGraph, jobs: JobInstance, flows: List[Flow],
              T: int = 2000, seed: int = 0, warmup: int = 0,
-             trace: bool = False, arrivals=None):
+             trace: bool = False, arrivals=None, mac: str = "share"):
     """Returns (mean_delay_per_job (J,), completed_counts (J,)); with
     ``trace=True`` also a dict of per-slot totals (arrivals, sink
     departures, packets in network — the reference ``plot_metrics``
     series, offloading_v3.py:588-607).  ``arrivals`` ((T, J) counts)
     replaces the seeded Poisson draws; ``draw_arrivals(jobs, T, seed)`` is
-    the stream ``seed`` alone would give."""
+    the stream ``seed`` alone would give.  ``mac`` is passed through to
+    ``simulate_routes``; the schedule dict of ``mac="mwis"`` is dropped."""
     J = jobs.num_jobs
     if arrivals is None:
         arrivals = draw_arrivals(jobs, T, seed)
@@ -264,7 +336,7 @@ def simulate(g: CaseGraph, jobs: JobInstance, flows: List[Flow],
     dst = np.array([f.dst for f in flows], dtype=np.int64)
 
     out = simulate_routes(g, jobs.ul, jobs.dl, dst, route_links, nhop,
-                          arrivals, warmup=warmup, trace=trace)
+                          arrivals, warmup=warmup, trace=trace, mac=mac)
     delay_sum, count = out[0], out[1]
     with np.errstate(invalid="ignore", divide="ignore"):
         mean_delay = np.where(count > 0, delay_sum / np.maximum(count, 1),
@@ -275,10 +347,11 @@ def simulate(g: CaseGraph, jobs: JobInstance, flows: List[Flow],
 
 
 def dump_case(path, g, ul, dl, dst, route_links, nhop, arrivals,
-              warmup: int = 0):
+              warmup: int = 0, mac: int = 0):
     """Flat binary dump of one ``simulate_routes`` case for the stand-alone
     host program (tests/host/timeslot_host.cpp): nine int32 header words
-    ``E N J H T warmup P nconf 0``, then conf_indptr (E+1) int32,
+    ``E N J H T warmup P nconf mac`` (``mac`` 0: share, 1: mwis, read by
+    tests/host/timeslot_mwis_host.cpp), then conf_indptr (E+1) int32,
     conf_indices int32, link_rates (E) fp32, proc_bws (N) fp32, arrivals
     (T,J) uint8, slot_off (T+1) int32, route_links (J,H) int32, nhop (J)
     int32, dst (J) int64, ul (J) fp32, dl (J) fp32.  The rates are rounded
@@ -295,7 +368,7 @@ def dump_case(path, g, ul, dl, dst, route_links, nhop, arrivals,
     cip = np.asarray(g.conf_indptr, dtype=np.int32)[:E + 1]
     cols = np.asarray(g.conf_indices, dtype=np.int32)[:cip[-1]]
     head = np.array([E, N, J, rl.shape[1], T, warmup, max(int(slot_off[-1]), 1),
-                     len(cols), 0], dtype=np.int32)
+                     len(cols), int(mac)], dtype=np.int32)
     with open(path, "wb") as f:
         for a in (head, cip, cols,
                   np.asarray(g.link_rates, dtype=np.float32)[:E],

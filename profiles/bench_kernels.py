@@ -12,7 +12,11 @@ Output: one JSON line per (config, stage) with mean µs over the timed reps.
 of the same instances on this host's CPU (whose outputs must equal the
 kernel's), with the ratio per batch.  ``--config timeslot_stats`` is the
 same configuration through the statistics entry point (``timeslot_sim_stats``,
-``simulate(stats=True)``).
+``simulate(stats=True)``).  ``--config timeslot_mwis`` and
+``--config timeslot_mwis_stats`` are the same batch through the scheduled-MAC
+entry points (``timeslot_sim_mwis``, ``timeslot_sim_mwis_stats``,
+``simulate(mac="mwis")``), with the rounds per slot the oracle's schedules
+took on the instances timed in Python.
 
 ``--config fixedpoint`` times the three kernels that are little else than
 the contention fixed point (actor_head_fwd, actor_head_bwd, critic) on the
@@ -169,7 +173,7 @@ def bench_config(name, nodes, batch, gtype, distinct, reps):
 
 
 def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
-                   py_instances=4, stats=False):
+                   py_instances=4, stats=False, mac="share"):
     import time
     from types import SimpleNamespace
 
@@ -179,9 +183,11 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
     from multihop_offload_amd.models.chebconv import ChebConvStack
     from multihop_offload_amd.harness.train_batched import build_training_cases
     from multihop_offload_amd.ops import dispatch
+    from multihop_offload_amd.sim import timeslot as ts
     from multihop_offload_amd.sim.timeslot import (num_delay_bins,
                                                    simulate_routes)
 
+    mwis = mac == "mwis"
     cases = build_training_cases(nodes, batch, 16, 1000, 7, gtype="ba",
                                  workers=8)
     model = ChebConvStack(K=2, dtype=torch.float32, seed=3)
@@ -191,7 +197,7 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
     jobs = eng.sample_jobs(load, gen)
     res = eng.baseline_episode(jobs)
     arr = eng.draw_arrivals(jobs, T_sim, gen)
-    sim = eng.simulate(jobs, res, arr, stats=stats)
+    sim = eng.simulate(jobs, res, arr, stats=stats, mac=mac)
     tasks = int(arr.sum())
 
     # the bare launch: the wrapper's prefix sums and error read left out
@@ -206,19 +212,31 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
             eng.k_conf_base, eng.k_conf_cols, eng.link_rates.contiguous(),
             eng.proc_bws.contiguous(), eng.T_arr.contiguous(), eng.k_E_arr,
             eng.k_N_arr, 0, pool, False)
-    launch = ext.timeslot_sim
+    launch = ext.timeslot_sim_mwis if mwis else ext.timeslot_sim
     if stats:
         args += (torch.floor(eng.T_arr).to(torch.int32),
                  num_delay_bins(T_sim))
-        launch = ext.timeslot_sim_stats
+        launch = ext.timeslot_sim_mwis_stats if mwis \
+            else ext.timeslot_sim_stats
     out = launch(*args)
     assert not bool(out[2].any())
     assert torch.equal(out[0], sim.delay_sum)
     if stats:
         assert torch.equal(out[6], sim.stats.delay_hist)
         assert torch.equal(out[9], sim.stats.qlen_sum)
+    if mwis:
+        assert torch.equal(out[-1], sim.sched_slots)
     kernel_us = timeit(lambda: launch(*args), reps)
-    call_us = timeit(lambda: eng.simulate(jobs, res, arr, stats=stats), reps)
+    call_us = timeit(lambda: eng.simulate(jobs, res, arr, stats=stats,
+                                          mac=mac), reps)
+    # every schedule the oracle computes below: rounds per slot
+    real_schedule, rounds = ts.mwis_schedule, []
+
+    def counting_schedule(cip, cols, w):
+        on, r = real_schedule(cip, cols, w)
+        rounds.append(r)
+        return on, r
+    ts.mwis_schedule = counting_schedule
 
     # the Python simulator on the first instances, same host, same inputs
     f64 = lambda x: x.cpu().numpy().astype(np.float64)   # noqa: E731
@@ -237,8 +255,14 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
              res.nhop[b, :k].cpu().numpy(), arr[b][:, :k].cpu().numpy())
         t0 = time.perf_counter()
         ds, ct, *st = simulate_routes(*a, stats=stats,
-                                      late_after=int(eng.T_arr[b]))
+                                      late_after=int(eng.T_arr[b]), mac=mac)
         t_py += time.perf_counter() - t0
+        if mwis:
+            sc = st.pop()
+            assert np.array_equal(
+                sc["sched_slots"],
+                sim.sched_slots[b, :g.num_links].cpu().numpy())
+            assert sc["rounds_max"] == max(rounds[-T_sim:])
         if stats:
             E = g.num_links
             assert np.array_equal(st[0]["delay_hist"],
@@ -251,12 +275,21 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
                 assert np.array_equal(st[0][key][E:], got[eng.E:]), key
         assert np.array_equal(ds, sim.delay_sum[b, :k].cpu().numpy())
         assert np.array_equal(ct, sim.count[b, :k].cpu().numpy())
+    ts.mwis_schedule = real_schedule
     py_s = t_py / py_instances
-    plan = (dispatch.timeslot_stats_lds_plan if stats
-            else dispatch.timeslot_lds_plan)(eng.N, eng.E, eng.Jmax)
+    if mwis:
+        plan = dispatch.timeslot_mwis_lds_plan(eng.N, eng.E, eng.Jmax, stats)
+        extra = {"rounds_mean_per_slot": round(float(np.mean(rounds)), 3),
+                 "rounds_max": int(max(rounds)),
+                 "rounds_instances": py_instances}
+    else:
+        plan = (dispatch.timeslot_stats_lds_plan if stats
+                else dispatch.timeslot_lds_plan)(eng.N, eng.E, eng.Jmax)
+        extra = {}
     print(json.dumps({
         "config": f"timeslot_b{batch}_n{nodes}",
-        "stage": "timeslot_sim_stats" if stats else "timeslot_sim",
+        "stage": "timeslot_sim" + ("_mwis" if mwis else "")
+        + ("_stats" if stats else ""),
         "B": eng.B, "N": eng.N, "E": eng.E, "J": eng.Jmax, "T": T_sim,
         "load": load, "tasks": tasks, "pool": pool,
         "lds_bytes": plan["lds_bytes"], "threads": plan["threads"],
@@ -266,7 +299,7 @@ def bench_timeslot(nodes=100, batch=256, load=0.15, T_sim=1000, reps=50,
         "python_s_per_batch": round(py_s * eng.B, 2),
         "ratio_python_over_kernel": round(py_s * eng.B / (kernel_us * 1e-6)),
         "ratio_python_over_call": round(py_s * eng.B / (call_us * 1e-6)),
-        "outputs_equal_python": True}), flush=True)
+        "outputs_equal_python": True, **extra}), flush=True)
 
 
 def bench_fixedpoint(batches=(256, 1024), budgets=(-1,), reps=200):
@@ -467,7 +500,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="both",
                     choices=["flagship", "er1000", "both", "timeslot",
-                             "timeslot_stats", "fixedpoint", "apsp",
+                             "timeslot_stats", "timeslot_mwis",
+                             "timeslot_mwis_stats", "fixedpoint", "apsp",
                              "cheb"])
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--budgets", type=str, default="-1",
@@ -486,6 +520,10 @@ if __name__ == "__main__":
         bench_timeslot(reps=args.reps)
     if args.config == "timeslot_stats":
         bench_timeslot(reps=args.reps, stats=True)
+    if args.config == "timeslot_mwis":
+        bench_timeslot(reps=args.reps, mac="mwis")
+    if args.config == "timeslot_mwis_stats":
+        bench_timeslot(reps=args.reps, stats=True, mac="mwis")
     if args.config in ("flagship", "both"):
         bench_config("flagship_b1024_n110", 110, 1024, "ba", 16, args.reps)
     if args.config in ("er1000", "both"):
