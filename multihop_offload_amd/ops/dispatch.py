@@ -88,6 +88,18 @@ def cheb_force_full_width(on: bool) -> None:
     _require_hip().cheb_force_full_width(bool(on))
 
 
+def cheb_lds_plan(Ee: int, K: int, max_nnz: int) -> dict:
+    """LDS plans of the LDS-resident ChebConv launchers for graphs of Ee
+    extended links, order K and at most ``max_nnz`` support entries: for each
+    of ``fwd``, ``bwd`` (the K<=2 kernels, plain and edge) and ``kn_fwd``,
+    ``kn_bwd`` (generic K) a dict of ``rows_pad``, ``lds_bytes``,
+    ``stage_csr`` (1: the support CSR is copied into LDS, 0: read from
+    global memory) and ``fits`` — the launcher's own plan, nothing is
+    launched."""
+    plan = _require_hip().cheb_lds_plan(int(Ee), int(K), int(max_nnz))
+    return {k: dict(v) for k, v in plan.items()}
+
+
 # the statistics of timeslot_sim(stats=True), in the extension's order
 STAT_KEYS = ("delay_max", "late", "delay_hist", "stuck", "stuck_age",
              "qlen_sum", "qlen_max", "busy_slots", "nb_sum")

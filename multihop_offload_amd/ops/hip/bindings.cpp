@@ -130,6 +130,7 @@ std::vector<torch::Tensor> cheb_kn_bwd_hip(
     torch::Tensor W, torch::Tensor ext_indptr, torch::Tensor ext_base,
     torch::Tensor ext_cols, long max_nnz);
 bool cheb_fits_lds(long Ee, long K);
+py::dict cheb_lds_plan_py(long Ee, long K, long max_nnz);
 void cheb_force_full_width(bool on);
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, bool>
 cheb_fwd_edge_hip(torch::Tensor x, torch::Tensor W, torch::Tensor bias,
@@ -197,6 +198,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("cheb_kn_fwd", &cheb_kn_fwd_hip);
     m.def("cheb_kn_bwd", &cheb_kn_bwd_hip);
     m.def("cheb_fits_lds", &cheb_fits_lds);
+    m.def("cheb_lds_plan", &cheb_lds_plan_py);
     m.def("fused_adam", &fused_adam_hip);
     m.def("cheb_large_fwd", &cheb_large_fwd_hip);
     m.def("cheb_large_bwd", &cheb_large_bwd_hip);

@@ -57,8 +57,14 @@ constexpr int KN_NBUF = 3;       // cheb_kn_*: Xb | Tb | Yb, Db | Pb | Qb
 constexpr int WGRAD_SPLIT = 2;
 
 // ---- fused layer tile: Xb <- act(X·W0 + T·W1 + b) -----------------------
-// Safe in place: every tile's A-operands read only the tile's own rows, so
-// writing the activated output back into those rows races nothing.
+// In place: the two column halves of a row tile read the same A operands,
+// all 32 columns of the tile's rows, so one wave owns both halves (as in
+// gemm_layer_first): it has read every operand before it writes, and no
+// other wave reads those rows.  With the halves on two waves and no barrier
+// between the tiles of a wave, the wave that finished its half first wrote
+// activated values into columns its neighbour was still reading (seen at
+// K = 1 from 19 row tiles on: wrong and run-to-run different lam).  Each
+// half keeps its k order, so the sums are bitwise what they were.
 DEV_INLINE void gemm_layer_fused(float* __restrict__ Xb,
                                  const float* __restrict__ Tb,
                                  const float* __restrict__ Wl,
@@ -67,35 +73,40 @@ DEV_INLINE void gemm_layer_fused(float* __restrict__ Xb,
     const int lane = tid & 63;
     const int wid = tid >> 6;
     const int nw = blockDim.x >> 6;
-    const int mtiles = rows_pad / 16;
     const int r_in = lane & 15;
     const int k_in = lane >> 4;
-    for (int t = wid; t < mtiles * 2; t += nw) {
-        const int mt = t >> 1;
-        const int c0 = (t & 1) * 16;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int mt = wid; mt < rows_pad / 16; mt += nw) {
+        f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int kk = 0; kk < F / 4; ++kk) {
             const int k = kk * 4 + k_in;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                Xb[(mt * 16 + r_in) * STRIDE + k], Wl[k * F + c0 + r_in],
-                acc, 0, 0, 0);
+            const float a = Xb[(mt * 16 + r_in) * STRIDE + k];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                    a, Wl[k * F + h * 16 + r_in], acc[h], 0, 0, 0);
         }
         if (K > 1) {
 #pragma unroll
             for (int kk = 0; kk < F / 4; ++kk) {
                 const int k = kk * 4 + k_in;
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    Tb[(mt * 16 + r_in) * STRIDE + k],
-                    Wl[F * F + k * F + c0 + r_in], acc, 0, 0, 0);
+                const float a = Tb[(mt * 16 + r_in) * STRIDE + k];
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+                    acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                        a, Wl[F * F + k * F + h * 16 + r_in], acc[h], 0, 0,
+                        0);
             }
         }
-        const int col = c0 + (lane & 15);
-        const float bv = bl[col];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = mt * 16 + (lane >> 4) * 4 + r;
-            Xb[row * STRIDE + col] = act(acc[r] + bv, last);
+        for (int h = 0; h < 2; ++h) {
+            const int col = h * 16 + (lane & 15);
+            const float bv = bl[col];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = mt * 16 + (lane >> 4) * 4 + r;
+                Xb[row * STRIDE + col] = act(acc[h][r] + bv, last);
+            }
         }
     }
 }
@@ -931,6 +942,25 @@ bool cheb_fits_lds(long Ee, long K) {
     const bool kn = K > 2;
     return cheb_lds_plan(Ee, K, kn ? KN_NBUF : FWD_NBUF, true, 0).fits &&
            cheb_lds_plan(Ee, K, kn ? KN_NBUF : BWD_NBUF, false, 0).fits;
+}
+
+// Host-only: the plan each LDS-resident launcher computes at this shape
+// (nothing is launched).  fwd/bwd are the K<=2 kernels (plain and edge share
+// a plan), kn_* the generic-K ones; the tests ask it whether a launch stages
+// the support CSR in LDS or reads it from global memory.
+py::dict cheb_lds_plan_py(long Ee, long K, long max_nnz) {
+    using namespace pybind11::literals;
+    auto row = [&](int nbuf, bool with_bias) {
+        const LdsPlan p = cheb_lds_plan((int)Ee, (int)K, nbuf, with_bias,
+                                        max_nnz);
+        return py::dict("rows_pad"_a = p.rows_pad,
+                        "lds_bytes"_a = (long)p.lds_bytes,
+                        "stage_csr"_a = p.stage_csr, "fits"_a = p.fits);
+    };
+    return py::dict("fwd"_a = row(FWD_NBUF, true),
+                    "bwd"_a = row(BWD_NBUF, false),
+                    "kn_fwd"_a = row(KN_NBUF, true),
+                    "kn_bwd"_a = row(KN_NBUF, false));
 }
 
 // cheb_force_full_width(true): every later cheb_fwd_edge launch takes the
