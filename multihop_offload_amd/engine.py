@@ -641,17 +641,20 @@ class EpisodeEngine:
         return dm, (lam, lam_c, mu_hist)
 
     def _actor_backward_native(self, saved, grad_edge, dm, unit_mtx,
-                               written):
+                               written, critic_loss=None):
         """Actor backward of the native-glue episode: the head's VJP with
         the cotangent assembled in the kernel (``grad_dist_matrix`` fused
         into ``actor_head_bwd``), then autograd through the ChebConv stack.
-        Returns loss_mse."""
+        Returns loss_mse, and with ``critic_loss`` (the critic's per-graph
+        loss) ``(loss_mse, loss_fn)``: its sum, taken in the kernel that
+        finishes loss_mse."""
         lam, lam_c, mu_hist = saved
-        dlam, loss_mse = ops.require_hip().actor_head_bwd_fused(
+        out = ops.require_hip().actor_head_bwd_fused(
             grad_edge.contiguous(), dm, unit_mtx, written, lam_c, mu_hist,
-            *self._actor_head_tables(), self.fp_iters, self.delay_clamp)
-        lam.backward(dlam)
-        return loss_mse
+            *self._actor_head_tables(), self.fp_iters, self.delay_clamp,
+            critic_loss)
+        lam.backward(out[0])
+        return out[1] if critic_loss is None else (out[1], out[2])
 
     def actor_forward(self, jobs: JobBatch):
         """features → ChebConv → λ → fixed point → delays → (B,N,N) delay
@@ -749,8 +752,9 @@ class EpisodeEngine:
             if expl_t is not None or prob:
                 self._rng_state[1] += 1
                 rng_t = self._rng_state
+            # uds goes in by its strides (the diagonal view of dm: no copy)
             dst, islocal = ext.decide(
-                sp.contiguous(), self.sp_hop.contiguous(), uds.contiguous(),
+                sp.contiguous(), self.sp_hop.contiguous(), uds,
                 self.k_servers, jobs.sources, jobs.mask,
                 jobs.ul.contiguous(), jobs.dl.contiguous(),
                 expl_t, rng_t, 1 if prob else 0)
@@ -861,9 +865,9 @@ class EpisodeEngine:
                 self.k_conf_cols, self.link_rates.contiguous(),
                 self.proc_bws.contiguous(), self.k_edges,
                 self.T_arr.contiguous(), self.k_E_arr, self.k_N_arr, H,
-                self.fp_iters)
+                self.fp_iters, self.overflow_total)
+            # the kernel adds its truncated walks to overflow_total itself
             self._last_overflow = overflow
-            self.overflow_total += overflow.sum().to(torch.int64)
             return rl, nhop, delay_emp, unit_mtx, written
         rl, nhop = self.route_walk(jobs, dst, sp)
         delay_emp, unit_mtx, written, *_ = self.evaluate(jobs, dst, rl, nhop)
@@ -972,26 +976,30 @@ class EpisodeEngine:
     # ------------------------------------------------------------- critic
     def critic_backward(self, jobs: JobBatch, dst: torch.Tensor,
                         route_links: torch.Tensor,
-                        nhop: Optional[torch.Tensor] = None):
+                        nhop: Optional[torch.Tensor] = None,
+                        per_graph: bool = False):
         """Critic loss over the routes tensor + grad wrt routes
         (gnn_offloading_agent.py:333-374) and the closed-form route-bias
         cotangent accumulation (:384-416), batched.  Returns
-        (grad_edge (B,Ē), loss_fn scalar)."""
+        (grad_edge (B,Ē), loss_fn scalar); with ``per_graph`` (HIP path
+        only) the loss stays (B,), for the caller to sum in a later
+        kernel."""
         B, E, Ee, J = self.B, self.E, self.Ee, self.Jmax
-        vedge_dst = self.node_vedge.gather(1, dst)            # (B,J)
         if self.use_hip and self.hip_critic_ok:
             from .ops import dispatch
             ext = dispatch.require_hip()
+            # the kernel looks the destinations' compute slots up itself
             grad_edge, loss = ext.critic(
                 route_links.contiguous(), nhop.contiguous(),
-                vedge_dst.contiguous(), jobs.mask,
+                dst.contiguous(), jobs.mask,
                 jobs.rates.contiguous(), jobs.ul.contiguous(),
                 jobs.dl.contiguous(), self.k_conf_indptr, self.k_conf_base,
                 self.k_conf_cols, self.link_rates.contiguous(),
                 self.bw_comp.contiguous(), self.k_E_arr,
                 self.T_arr.contiguous(), Ee,
-                self.fp_iters, self.delay_clamp)
-            return grad_edge, loss.sum()
+                self.fp_iters, self.delay_clamp, self.node_vedge)
+            return grad_edge, (loss if per_graph else loss.sum())
+        vedge_dst = self.node_vedge.gather(1, dst)            # (B,J)
         H = route_links.shape[2]
         valid = route_links >= 0
         safe = route_links.clamp(min=0)
@@ -1116,10 +1124,16 @@ class EpisodeEngine:
         loss_fn = loss_mse = None
         self.last_per_sample_grads = None
         if train:
-            grad_edge, loss_fn = self.critic_backward(jobs, dst, route_links,
-                                                      nhop)
+            # native path: the critic's loss stays per graph and is summed
+            # by the kernel that finishes loss_mse
+            fuse_sum = native_bwd and self.use_hip and self.hip_critic_ok
+            grad_edge, loss_fn = self.critic_backward(
+                jobs, dst, route_links, nhop, per_graph=fuse_sum)
             self.per_sample_request = per_sample
-            if native_bwd:
+            if fuse_sum:
+                loss_mse, loss_fn = self._actor_backward_native(
+                    actor_saved, grad_edge, dm, unit_mtx, written, loss_fn)
+            elif native_bwd:
                 loss_mse = self._actor_backward_native(
                     actor_saved, grad_edge, dm, unit_mtx, written)
             else:

@@ -88,6 +88,14 @@ def cheb_force_full_width(on: bool) -> None:
     _require_hip().cheb_force_full_width(bool(on))
 
 
+def adam_force_single_block(on: bool) -> None:
+    """Make every later ``fused_adam`` launch take the single-workgroup
+    kernel instead of the one-workgroup-per-tensor kernel (``False``
+    restores it).  A host-side switch for before/after timings and the
+    blocks-vs-single-block tests; the results are bit-equal either way."""
+    _require_hip().adam_force_single_block(bool(on))
+
+
 def cheb_lds_plan(Ee: int, K: int, max_nnz: int) -> dict:
     """LDS plans of the LDS-resident ChebConv launchers for graphs of Ee
     extended links, order K and at most ``max_nnz`` support entries: for each

@@ -197,6 +197,9 @@ class FusedAdam:
         self.m = _t.zeros_like(self.flat_p)
         self.v = _t.zeros_like(self.flat_p)
         self.step_dev = _t.zeros(1, dtype=_t.int32, device=dev)
+        # the kernel's blocks count themselves out here; the last one
+        # advances step_dev and leaves 0 (scratch, not optimizer state)
+        self._ticket = _t.zeros(1, dtype=_t.int32, device=dev)
         segs = []
         off = 0
         with _t.no_grad():
@@ -225,7 +228,8 @@ class FusedAdam:
         ext = dispatch.require_hip()
         ext.fused_adam(self.flat_p, self.flat_g, self.m, self.v, self.seg,
                        self.step_dev, scale, self.lr, self.betas[0],
-                       self.betas[1], self.eps, self.constraints)
+                       self.betas[1], self.eps, self.constraints,
+                       self._ticket)
 
     # -- snapshot/restore (guard rollbacks, resume) ---------------------------
     def state_dict(self):

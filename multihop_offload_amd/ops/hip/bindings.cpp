@@ -17,14 +17,14 @@ std::vector<torch::Tensor> walk_eval_hip(
     torch::Tensor conf_base, torch::Tensor conf_cols, torch::Tensor rates,
     torch::Tensor bw, torch::Tensor edges, torch::Tensor T_arr,
     torch::Tensor E_arr, torch::Tensor n_arr, long H,
-    long fp_iters);
+    long fp_iters, c10::optional<torch::Tensor> overflow_total);
 std::vector<torch::Tensor> critic_hip(
     torch::Tensor route_links, torch::Tensor nhop, torch::Tensor vedge_dst,
     torch::Tensor mask, torch::Tensor rate, torch::Tensor ul,
     torch::Tensor dl, torch::Tensor conf_indptr, torch::Tensor conf_base,
     torch::Tensor conf_cols, torch::Tensor rates, torch::Tensor bw_comp,
     torch::Tensor E_arr, torch::Tensor T_arr, long Ee, long iters,
-    double cap);
+    double cap, c10::optional<torch::Tensor> node_vedge);
 std::vector<torch::Tensor> actor_head_fwd_hip(
     torch::Tensor lam_ext, torch::Tensor conf_indptr,
     torch::Tensor conf_base, torch::Tensor conf_cols, torch::Tensor rates,
@@ -43,7 +43,8 @@ std::vector<torch::Tensor> actor_head_bwd_fused_hip(
     torch::Tensor conf_indptr, torch::Tensor conf_base,
     torch::Tensor conf_cols, torch::Tensor rates, torch::Tensor bw_comp,
     torch::Tensor edges, torch::Tensor node_vedge, torch::Tensor T_arr,
-    torch::Tensor E_arr, long iters, double cap);
+    torch::Tensor E_arr, long iters, double cap,
+    c10::optional<torch::Tensor> critic_loss);
 torch::Tensor floyd_warshall_dm_hip(torch::Tensor dm, torch::Tensor adj,
                                     c10::optional<torch::Tensor> n_arr);
 void fw_force_inplace(bool on);
@@ -158,16 +159,38 @@ std::vector<torch::Tensor> cheb_large_bwd_hip(
 void fused_adam_hip(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                     torch::Tensor v, torch::Tensor seg, torch::Tensor step,
                     double scale, double lr, double beta1, double beta2,
-                    double eps, bool constraints);
+                    double eps, bool constraints,
+                    c10::optional<torch::Tensor> ticket);
+void adam_force_single_block(bool on);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("floyd_warshall", &floyd_warshall_hip);
     m.def("decide", &decide_hip);
-    m.def("walk_eval", &walk_eval_hip);
-    m.def("critic", &critic_hip);
+    m.def("walk_eval", &walk_eval_hip, py::arg("sp"), py::arg("src"),
+          py::arg("dst"), py::arg("mask"), py::arg("rate"), py::arg("ul"),
+          py::arg("dl"), py::arg("adj_indptr"), py::arg("adj_idx"),
+          py::arg("adj_link"), py::arg("conf_indptr"), py::arg("conf_base"),
+          py::arg("conf_cols"), py::arg("rates"), py::arg("bw"),
+          py::arg("edges"), py::arg("T_arr"), py::arg("E_arr"),
+          py::arg("n_arr"), py::arg("H"), py::arg("fp_iters"),
+          py::arg("overflow_total") = py::none());
+    m.def("critic", &critic_hip, py::arg("route_links"), py::arg("nhop"),
+          py::arg("vedge_dst"), py::arg("mask"), py::arg("rate"),
+          py::arg("ul"), py::arg("dl"), py::arg("conf_indptr"),
+          py::arg("conf_base"), py::arg("conf_cols"), py::arg("rates"),
+          py::arg("bw_comp"), py::arg("E_arr"), py::arg("T_arr"),
+          py::arg("Ee"), py::arg("iters"), py::arg("cap"),
+          py::arg("node_vedge") = py::none());
     m.def("actor_head_fwd", &actor_head_fwd_hip);
     m.def("actor_head_bwd", &actor_head_bwd_hip);
-    m.def("actor_head_bwd_fused", &actor_head_bwd_fused_hip);
+    m.def("actor_head_bwd_fused", &actor_head_bwd_fused_hip,
+          py::arg("grad_edge"), py::arg("dm"), py::arg("unit_mtx"),
+          py::arg("written"), py::arg("lam_ext"), py::arg("mu_hist"),
+          py::arg("conf_indptr"), py::arg("conf_base"), py::arg("conf_cols"),
+          py::arg("rates"), py::arg("bw_comp"), py::arg("edges"),
+          py::arg("node_vedge"), py::arg("T_arr"), py::arg("E_arr"),
+          py::arg("iters"), py::arg("cap"),
+          py::arg("critic_loss") = py::none());
     m.def("floyd_warshall_dm", &floyd_warshall_dm_hip);
     m.def("fw_force_inplace", &fw_force_inplace);
     m.def("fw_register_rows", &fw_register_rows);
@@ -199,7 +222,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("cheb_kn_bwd", &cheb_kn_bwd_hip);
     m.def("cheb_fits_lds", &cheb_fits_lds);
     m.def("cheb_lds_plan", &cheb_lds_plan_py);
-    m.def("fused_adam", &fused_adam_hip);
+    m.def("fused_adam", &fused_adam_hip, py::arg("p"), py::arg("g"),
+          py::arg("m"), py::arg("v"), py::arg("seg"), py::arg("step"),
+          py::arg("scale"), py::arg("lr"), py::arg("beta1"),
+          py::arg("beta2"), py::arg("eps"), py::arg("constraints"),
+          py::arg("ticket") = py::none());
+    m.def("adam_force_single_block", &adam_force_single_block);
     m.def("cheb_large_fwd", &cheb_large_fwd_hip);
     m.def("cheb_large_bwd", &cheb_large_bwd_hip);
 }

@@ -85,7 +85,9 @@ DEV_INLINE f32x4 wgrad_tile(const float* __restrict__ src,
 
 // 2×2 output tiles of 16×16, each over SPLIT equal row ranges (rows a
 // multiple of 4*SPLIT); one (tile, range) per wave.  The ranges and the row
-// tiles of a graph combine through global fp32 atomics (dW is prezeroed).
+// tiles of a graph combine through global fp32 atomics (dW is zero by
+// then: the K<=2 backward zeroes its own slice, the other launchers fill
+// it).
 template <int SPLIT>
 DEV_INLINE void wgrad_rows(const float* __restrict__ src,
                            const float* __restrict__ delta,
@@ -181,7 +183,7 @@ DEV_INLINE void mask_rows(float* __restrict__ D,
 }
 
 // ---- db[j] += sum_r D[r][j] over `rows` LDS rows -------------------------
-// (column, row-chunk) threads, one atomic per thread; db is prezeroed.
+// (column, row-chunk) threads, one atomic per thread; db is zero by then, like dW.
 // The chunk order of the atomics is not fixed, so db is reproducible only
 // to the last bits.
 DEV_INLINE void db_colsum(const float* __restrict__ D, int rows,

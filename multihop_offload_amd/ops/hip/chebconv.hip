@@ -33,8 +33,8 @@
 //     32-column SpMV.
 //   backward, layer 0: X_0 from x and T1_0 4 wide; weight gradients as in
 //     the last layer, over the i0 = 0 tiles.
-// dW / db cells outside the real shapes are never written and stay the
-// zeros of the prezeroed buffers.  Any other width, the old entry points
+// dW / db cells outside the real shapes are never written again and stay
+// the zeros the backward kernel stores at its top.  Any other width, the old entry points
 // and cheb_force_full_width(true) run the full-width path.
 
 #include <hip/hip_runtime.h>
@@ -439,7 +439,7 @@ DEV_INLINE void load_top_delta_edge(float* __restrict__ Db,
     }
 }
 
-// db[0] = sum_r D[r][0]: one wave, one plain store (db is prezeroed and the
+// db[0] = sum_r D[r][0]: one wave, one plain store (db was zeroed and the
 // cell has this one writer)
 DEV_INLINE void db_col0(const float* __restrict__ D, int rows,
                         float* __restrict__ db_out, int tid) {
@@ -636,8 +636,8 @@ __global__ void cheb_bwd_kernel(
     const int* __restrict__ ext_indptr,
     const long* __restrict__ ext_base,
     const int* __restrict__ ext_cols,
-    float* __restrict__ dW,              // (B,L,K,32,32) out (prezeroed)
-    float* __restrict__ db,              // (B,L,32) out (prezeroed)
+    float* __restrict__ dW,              // (B,L,K,32,32) out
+    float* __restrict__ db,              // (B,L,32) out
     int Ee, int L, int K, int rows_pad, int stage_csr, int stage_mask) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* Ab = reinterpret_cast<float*>(smem_raw);   // X_l, later dX
@@ -647,13 +647,24 @@ __global__ void cheb_bwd_kernel(
 
     const int b = blockIdx.x;
     const int tid = threadIdx.x, nt = blockDim.x;
+    float* dWb = dW + (size_t)b * L * K * F * F;
+    float* dbb = db + (size_t)b * L * F;
+    // dW / db arrive torch::empty: the workgroup zeroes its own slice (the
+    // atomic adds and the cells outside an edge layer's real shape need it)
+    // with stores nothing waits for; the first add is behind a barrier.
+    // Both slices are whole float4s (F = 32).
+    {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4* w4 = reinterpret_cast<float4*>(dWb);
+        for (int i = tid; i < L * K * F * F / 4; i += nt) w4[i] = z;
+        float4* b4 = reinterpret_cast<float4*>(dbb);
+        for (int i = tid; i < L * F / 4; i += nt) b4[i] = z;
+    }
     const int *ipt, *cls;
     graph_csr(ext_indptr, ext_base, ext_cols, b, Ee, stage_csr,
               reinterpret_cast<int*>(Wl + (size_t)K * F * F), tid, nt, ipt,
               cls);
     const float* actsb = acts + (size_t)b * (L + 1) * Ee * F;
-    float* dWb = dW + (size_t)b * L * K * F * F;
-    float* dbb = db + (size_t)b * L * F;
 
     if (EDGE) {
         // ---- last layer: the delta has one live column
@@ -1090,8 +1101,9 @@ std::vector<torch::Tensor> cheb_bwd_edge_hip_mask(
                     "forward expected");
     const LdsPlan plan = cheb_lds_plan(Ee, K, BWD_NBUF, false, max_nnz);
     TORCH_CHECK(plan.fits, "graph too large for fused ChebConv bwd");
-    auto dW = torch::zeros({B, L, K, F, F}, dlam.options());
-    auto db = torch::zeros({B, L, F}, dlam.options());
+    // each workgroup zeroes its own slice: no fill launches
+    auto dW = torch::empty({B, L, K, F, F}, dlam.options());
+    auto db = torch::empty({B, L, F}, dlam.options());
     auto stream = at::cuda::getCurrentCUDAStream();
     hipLaunchKernelGGL(edge ? cheb_bwd_kernel<true> : cheb_bwd_kernel<false>,
                        dim3(B), dim3(512), plan.lds_bytes, stream.stream(),

@@ -39,14 +39,14 @@ DEV_INLINE float u01(unsigned long long h) {
 
 // cost of offloading a job to server node sv: uplink + downlink along the
 // shortest path (floored at the hop count) + compute; sp_row/hop_row are
-// the rows of the job's source
+// the rows of the job's source, uds the graph's row with element stride us
 DEV_INLINE float server_cost(const float* sp_row, const float* hop_row,
-                             const float* uds, int sv, float ulj,
+                             const float* uds, long us, int sv, float ulj,
                              float dlj) {
     const float spv = sp_row[sv];
     const float hpv = hop_row[sv];
     return fmax1(spv * ulj, hpv) + fmax1(spv * dlj, hpv)
-           + fmax1(uds[sv] * ulj, 1.0f);
+           + fmax1(uds[sv * us] * ulj, 1.0f);
 }
 
 // unnormalised softmax weight of a cost; a non-finite cost weighs nothing
@@ -62,7 +62,8 @@ DEV_INLINE float softmax_w(float c, float cmax) {
 __global__ void decide_kernel(
     const float* __restrict__ sp,       // (B,N,N) diag=0
     const float* __restrict__ hop,      // (B,N,N)
-    const float* __restrict__ uds,      // (B,N)   inf at relays
+    const float* __restrict__ uds,      // (B,N)   inf at relays, by its
+    long uds_sb, long uds_sn,           //         strides (dm's diagonal)
     const int* __restrict__ servers,    // (B,S)   pad -1 (tail-contiguous)
     const long* __restrict__ src,       // (B,J)
     const bool* __restrict__ mask,      // (B,J)
@@ -76,7 +77,7 @@ __global__ void decide_kernel(
     const int b = blockIdx.x;
     const float* spb = sp + (size_t)b * N * N;
     const float* hpb = hop + (size_t)b * N * N;
-    const float* udsb = uds + (size_t)b * N;
+    const float* udsb = uds + (size_t)b * uds_sb;
     const int* srvb = servers + (size_t)b * S;
     const float eps = explore ? *explore : 0.0f;
     const unsigned long long key =
@@ -89,7 +90,7 @@ __global__ void decide_kernel(
         const int s0 = (int)src[bj];
         if (!mask[bj]) { dst_out[bj] = s0; islocal_out[bj] = true; continue; }
         const float ulj = ul[bj], dlj = dl[bj];
-        const float local = udsb[s0] * ulj;
+        const float local = udsb[s0 * uds_sn] * ulj;
         const float* sp_row = spb + (size_t)s0 * N;
         const float* hop_row = hpb + (size_t)s0 * N;
         int best_s;
@@ -103,7 +104,7 @@ __global__ void decide_kernel(
             for (int s = 0; s < S; ++s) {
                 const int sv = srvb[s];
                 if (sv < 0) continue;
-                float c = server_cost(sp_row, hop_row, udsb, sv, ulj, dlj);
+                float c = server_cost(sp_row, hop_row, udsb, uds_sn, sv, ulj, dlj);
                 if (isfinite(c)) { c = c < 1e30f ? c : 1e30f;
                                    cmax = c > cmax ? c : cmax; }
             }
@@ -112,7 +113,7 @@ __global__ void decide_kernel(
                 const int sv = srvb[s];
                 if (sv < 0) continue;
                 psum += softmax_w(
-                    server_cost(sp_row, hop_row, udsb, sv, ulj, dlj), cmax);
+                    server_cost(sp_row, hop_row, udsb, uds_sn, sv, ulj, dlj), cmax);
             }
             psum += softmax_w(local, cmax);
             const float r = u01(mix64(key ^ (unsigned long long)bj)) * psum;
@@ -122,7 +123,7 @@ __global__ void decide_kernel(
                 const int sv = srvb[s];
                 if (sv < 0) continue;
                 acc += softmax_w(
-                    server_cost(sp_row, hop_row, udsb, sv, ulj, dlj), cmax);
+                    server_cost(sp_row, hop_row, udsb, uds_sn, sv, ulj, dlj), cmax);
                 if (r < acc) { best_s = s; break; }
             }
         } else {
@@ -135,7 +136,7 @@ __global__ void decide_kernel(
                 const int sv = srvb[s];
                 if (sv < 0) continue;
                 const float c =
-                    server_cost(sp_row, hop_row, udsb, sv, ulj, dlj);
+                    server_cost(sp_row, hop_row, udsb, uds_sn, sv, ulj, dlj);
                 if (c < best) { best = c; best_s = s; }
             }
             if (local < best) best_s = -1;      // -1 = local
@@ -166,7 +167,15 @@ __global__ void decide_kernel(
 // (job_index+1) << 32 | float_bits(unit) into a u64 scratch cell with
 // atomicMax (units are finite non-negative, so the job index dominates),
 // then unpacking after a barrier — block b owns slice b, so no cross-block
-// coherence is needed.
+// coherence is needed.  Only a graph's links and its diagonal can be
+// written, so the scratch has one cell per link and one per node (link l at
+// l, node n at E + n), not one per matrix cell: stage 3 packs once per hop,
+// stage 3b writes the (u,v), (v,u) and (n,n) cells of the non-zero packs
+// into unit_mtx/written, which the workgroup zero-fills at its top with
+// plain stores that nothing waits for.
+//
+// overflow[b] is counted in LDS and stored once; a non-zero count is also
+// added to the optional device-side total, so the caller needs no reduction.
 // ---------------------------------------------------------------------------
 __global__ void walk_eval_kernel(
     const float* __restrict__ sp,        // (B,N,N)
@@ -184,10 +193,11 @@ __global__ void walk_eval_kernel(
     int* __restrict__ route_links,       // (B,J,H) out, -1 pad
     int* __restrict__ nhop,              // (B,J) out
     float* __restrict__ delay_emp,       // (B,J) out (nan for padded jobs)
-    float* __restrict__ unit_mtx,        // (B,N,N) out (prezeroed)
-    bool* __restrict__ written,          // (B,N,N) out (prezeroed)
-    unsigned long long* __restrict__ upack,  // (B,N,N) scratch
+    float* __restrict__ unit_mtx,        // (B,N,N) out
+    bool* __restrict__ written,          // (B,N,N) out
+    unsigned long long* __restrict__ upack,  // (B,E+N) scratch
     int* __restrict__ overflow,          // (B) out
+    unsigned long long* __restrict__ overflow_total,  // () += | nullptr
     const int* __restrict__ n_arr,       // (B) real node counts (padding)
     const qm::WalkPlan p, int stage_budget, int N, int E, int J, int H,
     int fp_iters) {
@@ -197,6 +207,7 @@ __global__ void walk_eval_kernel(
     float* mu = lds + p.mu;
     float* busy = lds + p.busy;
     float* sload = lds + p.sload;
+    __shared__ int ovf_s;                // truncated walks of this graph
 
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
@@ -206,7 +217,9 @@ __global__ void walk_eval_kernel(
     const int* aix = adj_idx + (size_t)b * 2 * E;
     const int* alk = adj_link + (size_t)b * 2 * E;
     const qm::Graph g = qm::graph_view(t, b);
-    unsigned long long* upk = upack + (size_t)b * N * N;
+    unsigned long long* upk = upack + (size_t)b * (E + N);
+    float* um = unit_mtx + (size_t)b * N * N;
+    bool* wm = written + (size_t)b * N * N;
     // per-graph effective sizes: padded link slots / inert pad nodes are
     // isolated and never touched by routes, so every E/N-length loop below
     // runs on the real extent only (ragged-E batches, pad_to mixed-N)
@@ -219,8 +232,21 @@ __global__ void walk_eval_kernel(
 
     for (int e = tid; e < Eb; e += nt) lam[e] = 0.0f;
     for (int n = tid; n < nb_; n += nt) sload[n] = 0.0f;
-    for (int i = tid; i < nb_ * nb_; i += nt)
-        upk[(i / nb_) * N + (i % nb_)] = 0ull;
+    for (int i = tid; i < E + N; i += nt) upk[i] = 0ull;
+    if (tid == 0) ovf_s = 0;
+    // outputs arrive torch::empty: zero the whole slice (pad rows and
+    // columns stay 0/false), stage 3b overwrites the written cells after
+    // the barriers below.  16-byte stores when every slice is aligned.
+    if (((N * N) & 15) == 0) {
+        float4* um4 = reinterpret_cast<float4*>(um);
+        uint4* wm4 = reinterpret_cast<uint4*>(wm);
+        for (int i = tid; i < N * N / 4; i += nt)
+            um4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int i = tid; i < N * N / 16; i += nt)
+            wm4[i] = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        for (int i = tid; i < N * N; i += nt) { um[i] = 0.f; wm[i] = false; }
+    }
     __syncthreads();
 
     // ---- stage 1: walk + load accumulation -------------------------------
@@ -254,7 +280,7 @@ __global__ void walk_eval_kernel(
             node = bestn;
             ++h;
         }
-        if (node != d) atomicAdd(&overflow[b], 1);
+        if (node != d) atomicAdd(&ovf_s, 1);
         nhop[bj] = h;
         for (int h2 = h; h2 < H; ++h2)       // outputs arrive torch::empty
             route_links[bj * H + h2] = -1;
@@ -280,33 +306,41 @@ __global__ void walk_eval_kernel(
             const int l = route_links[((size_t)b * J + j) * H + h];
             if (l < 0) break;
             const float unit = qm::emp_unit(lam[l], mu[l], g.T, tot);
-            const int u = edg[l * 2], v = edg[l * 2 + 1];
-            const unsigned long long pk = jtag | (unsigned long long)
-                __float_as_uint(unit);
-            atomicMax(&upk[(size_t)u * N + v], pk);
-            atomicMax(&upk[(size_t)v * N + u], pk);
+            atomicMax(&upk[l], jtag | (unsigned long long)
+                                   __float_as_uint(unit));
             acc += fmax1(ulj * unit, nh) + fmax1(dlj * unit, nh);
         }
         const int d = (int)dstv[bj];
         const float sunit = qm::emp_unit(sload[d], g.bw[d], g.T, ulj);
-        atomicMax(&upk[(size_t)d * N + d],
+        atomicMax(&upk[E + d],
                   jtag | (unsigned long long)__float_as_uint(sunit));
         acc += fmax1(ulj * sunit, 1.0f);
         delay_emp[bj] = acc;
     }
     __syncthreads();
     // ---- stage 3b: unpack last-job-wins units into unit_mtx/written ------
-    float* um = unit_mtx + (size_t)b * N * N;
-    bool* wm = written + (size_t)b * N * N;
-    // outputs arrive torch::empty: every cell is written exactly once
-    // (pad region → 0/false), replacing two fill launches per call
-    for (int i = tid; i < N * N; i += nt) {
-        const int r = i / N, c = i % N;
-        const unsigned long long pk =
-            (r < nb_ && c < nb_) ? upk[i] : 0ull;
-        um[i] = pk ? __uint_as_float((unsigned int)(pk & 0xffffffffull))
-                   : 0.f;
-        wm[i] = pk != 0ull;
+    for (int e = tid; e < Eb; e += nt) {
+        const unsigned long long pk = upk[e];
+        if (!pk) continue;
+        const float unit = __uint_as_float((unsigned int)(pk & 0xffffffffull));
+        const int u = edg[e * 2], v = edg[e * 2 + 1];
+        um[(size_t)u * N + v] = unit;
+        um[(size_t)v * N + u] = unit;
+        wm[(size_t)u * N + v] = true;
+        wm[(size_t)v * N + u] = true;
+    }
+    for (int n = tid; n < nb_; n += nt) {
+        const unsigned long long pk = upk[E + n];
+        if (!pk) continue;
+        um[(size_t)n * N + n] =
+            __uint_as_float((unsigned int)(pk & 0xffffffffull));
+        wm[(size_t)n * N + n] = true;
+    }
+    if (tid == 0) {
+        const int cnt = ovf_s;
+        overflow[b] = cnt;
+        if (cnt && overflow_total)
+            atomicAdd(overflow_total, (unsigned long long)cnt);
     }
 }
 
@@ -320,6 +354,11 @@ std::vector<torch::Tensor> decide_hip(
     long prob) {
     const int B = sp.size(0), N = sp.size(1);
     const int J = src.size(1), S = servers.size(1);
+    // uds is read through its strides: the diagonal view of the delay
+    // matrix (strides N², N + 1) needs no copy
+    TORCH_CHECK(uds.dim() == 2 && uds.size(0) == B && uds.size(1) == N
+                && uds.scalar_type() == torch::kFloat32,
+                "decide: uds is (B,N) fp32");
     auto dst = torch::empty({B, J}, src.options());
     auto islocal = torch::empty({B, J}, mask.options());
     const float* ep = explore.has_value()
@@ -328,7 +367,8 @@ std::vector<torch::Tensor> decide_hip(
     auto stream = at::cuda::getCurrentCUDAStream();
     hipLaunchKernelGGL(decide_kernel, dim3(B), dim3(256), 0, stream.stream(),
                        sp.data_ptr<float>(), hop.data_ptr<float>(),
-                       uds.data_ptr<float>(),
+                       uds.data_ptr<float>(), (long)uds.stride(0),
+                       (long)uds.stride(1),
                        servers.data_ptr<int>(), src.data_ptr<long>(),
                        mask.data_ptr<bool>(), ul.data_ptr<float>(),
                        dl.data_ptr<float>(), ep, rp,
@@ -345,9 +385,18 @@ std::vector<torch::Tensor> walk_eval_hip(
     torch::Tensor conf_base, torch::Tensor conf_cols, torch::Tensor rates,
     torch::Tensor bw, torch::Tensor edges, torch::Tensor T_arr,
     torch::Tensor E_arr, torch::Tensor n_arr, long H,
-    long fp_iters) {
+    long fp_iters, c10::optional<torch::Tensor> overflow_total) {
     const int B = sp.size(0), N = sp.size(1);
     const int J = src.size(1), E = rates.size(1);
+    unsigned long long* ovf_total = nullptr;
+    if (overflow_total.has_value()) {
+        TORCH_CHECK(overflow_total->scalar_type() == torch::kInt64
+                    && overflow_total->numel() == 1
+                    && overflow_total->is_cuda(),
+                    "walk_eval: overflow_total is one int64 on the device");
+        ovf_total = reinterpret_cast<unsigned long long*>(
+            overflow_total->data_ptr<long>());
+    }
     auto opts_i = adj_indptr.options();
     auto opts_f = sp.options();
     // all outputs fully initialized in-kernel (no fill launches)
@@ -356,10 +405,10 @@ std::vector<torch::Tensor> walk_eval_hip(
     auto delay_emp = torch::empty({B, J}, opts_f);
     auto unit_mtx = torch::empty({B, N, N}, opts_f);
     auto written = torch::empty({B, N, N}, opts_f.dtype(torch::kBool));
-    // u64 scratch for deterministic last-job-wins unit writes (the kernel
-    // zeroes its own slice — empty, not zeros)
-    auto upack = torch::empty({B, N, N}, opts_f.dtype(torch::kInt64));
-    auto overflow = torch::zeros({B}, opts_i.dtype(torch::kInt32));
+    // u64 scratch for deterministic last-job-wins unit writes, one cell per
+    // link and per node (the kernel zeroes its own slice — empty, not zeros)
+    auto upack = torch::empty({B, E + N}, opts_f.dtype(torch::kInt64));
+    auto overflow = torch::empty({B}, opts_i.dtype(torch::kInt32));
     const qm::WalkPlan p = qm::walk_plan(N, E);
     TORCH_CHECK(p.fits, "graph too large for LDS walk_eval");
     auto stream = at::cuda::getCurrentCUDAStream();
@@ -380,7 +429,8 @@ std::vector<torch::Tensor> walk_eval_hip(
                        unit_mtx.data_ptr<float>(), written.data_ptr<bool>(),
                        reinterpret_cast<unsigned long long*>(
                            upack.data_ptr<long>()),
-                       overflow.data_ptr<int>(), n_arr.data_ptr<int>(), p,
+                       overflow.data_ptr<int>(), ovf_total,
+                       n_arr.data_ptr<int>(), p,
                        budget, N, E, J, (int)H, (int)fp_iters);
     return {route_links, nhop, delay_emp, unit_mtx, written, overflow};
 }

@@ -34,7 +34,8 @@ using namespace qm;
 __global__ void critic_kernel(
     const int* __restrict__ route_links,   // (B,J,H) -1 pad
     const int* __restrict__ nhop,          // (B,J)
-    const long* __restrict__ vedge_dst,    // (B,J)
+    const long* __restrict__ vedge_dst,    // (B,J) slots | nodes (node_vedge)
+    const long* __restrict__ node_vedge,   // (B,N) | nullptr
     const bool* __restrict__ mask,         // (B,J)
     const float* __restrict__ rate,        // (B,J)
     const float* __restrict__ ul,          // (B,J)
@@ -48,11 +49,18 @@ __global__ void critic_kernel(
     const CriticPlan p,
     float cap,                             // delay clamp (0 = off)
     int stage_budget,                      // CSR staging bytes (0 = none)
-    int E, int C, int Ee, int J, int H, int iters) {
+    int E, int C, int Ee, int J, int H, int iters, int N) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* lds = reinterpret_cast<float*>(smem_raw);
     const int b = blockIdx.x;
     const int tid = threadIdx.x, nt = blockDim.x;
+    // the compute slot of job bj's destination: handed in, or looked up
+    // from the destination node
+    const long* nvb = node_vedge ? node_vedge + (size_t)b * N : nullptr;
+    auto dst_slot = [&](size_t bj) {
+        const long d = vedge_dst[bj];
+        return (int)(nvb ? nvb[d] : d);
+    };
     // large graphs (e.g. 1000-node ER): reverse-pass accumulators and the mu
     // history live in global scratch (same-CU coherence through
     // __syncthreads suffices — one workgroup per graph)
@@ -90,7 +98,7 @@ __global__ void critic_kernel(
             if (l < 0) break;
             atomicAdd(&lam_e[l], load);
         }
-        atomicAdd(&lam_e[(int)vedge_dst[bj]], load);
+        atomicAdd(&lam_e[dst_slot(bj)], load);
     }
     __syncthreads();
 
@@ -112,7 +120,7 @@ __global__ void critic_kernel(
         const int nh = nhop[bj];
         for (int h = 0; h <= nh; ++h) {
             const int e = (h < nh) ? route_links[bj * H + h]
-                                   : (int)vedge_dst[bj];
+                                   : dst_slot(bj);
             if (e < 0) break;
             const float x = data * unit[e];
             lloc += x > 1.f ? x : 1.f;
@@ -153,7 +161,7 @@ __global__ void critic_kernel(
         float run = 0.f;
         for (int h = 0; h <= nh; ++h) {
             const int e = (h < nh) ? route_links[bj * H + h]
-                                   : (int)vedge_dst[bj];
+                                   : dst_slot(bj);
             if (e < 0) break;
             const float x = data * unit[e];
             const float wx = x > 1.f ? 1.f : (x < 1.f ? 0.f : 0.5f);
@@ -286,30 +294,40 @@ struct FusedCot {
     }
 };
 
-// loss_mse = Σ_b Σ diff² / max(Σ_b count, 1), one block
+// loss_mse = Σ_b Σ diff² / max(Σ_b count, 1), one block; with `loss`
+// (the critic's per-graph loss) also loss_fn = Σ_b loss[b] from the same
+// strided partials and 256-wide tree
 __global__ void mse_finish_kernel(const float* __restrict__ mse_sq,
-                                  const int* __restrict__ mse_cnt, int B,
-                                  float* __restrict__ out) {
+                                  const int* __restrict__ mse_cnt,
+                                  const float* __restrict__ loss, int B,
+                                  float* __restrict__ out,
+                                  float* __restrict__ loss_out) {
     __shared__ float s_sq[256];
+    __shared__ float s_ls[256];
     __shared__ long long s_cnt[256];       // integer count, like torch's
-    float sq = 0.f;
+    float sq = 0.f, ls = 0.f;
     long long cnt = 0;
     for (int b = threadIdx.x; b < B; b += 256) {
         sq += mse_sq[b];
         cnt += mse_cnt[b];
+        if (loss) ls += loss[b];
     }
     s_sq[threadIdx.x] = sq;
+    s_ls[threadIdx.x] = ls;
     s_cnt[threadIdx.x] = cnt;
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
         if (threadIdx.x < w) {
             s_sq[threadIdx.x] += s_sq[threadIdx.x + w];
+            s_ls[threadIdx.x] += s_ls[threadIdx.x + w];
             s_cnt[threadIdx.x] += s_cnt[threadIdx.x + w];
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0)
+    if (threadIdx.x == 0) {
         out[0] = s_sq[0] / (float)(s_cnt[0] > 1 ? s_cnt[0] : 1);
+        if (loss) loss_out[0] = s_ls[0];
+    }
 }
 
 // actor head backward: cotangent on dm (dense or fused, see above) → δλ_ext
@@ -344,6 +362,10 @@ __global__ void actor_head_bwd_kernel(
     float sq = 0.f;                        // FusedCot's anchor error
     int cnt = 0;
 
+    // dlam_ext arrives torch::empty: the link part is written whole below,
+    // the node part only at the slots that exist — zero [E, Ee) here, before
+    // the first barrier (a graph with fewer computing nodes, a padded tail)
+    for (int e = E + tid; e < Ee; e += nt) out[e] = 0.f;
     for (int e = tid; e < g.Eb; e += nt) lam[e] = le[e];
     if (!p.large) {
         float* h = lds + p.hist;
@@ -383,10 +405,6 @@ __global__ void actor_head_bwd_kernel(
             out[ve] = dl_;
         }
     }
-    // padded tail (if any) stays whatever it was — zero it for safety
-    for (int e = tid; e < Ee; e += nt) {
-        if (e >= E + C) out[e] = 0.f;
-    }
     // s1 / s2 were last read inside fixed_point_bwd, behind its barrier
     cot.finish(b, sq, cnt, s1, s2);
 }
@@ -399,10 +417,23 @@ std::vector<torch::Tensor> critic_hip(
     torch::Tensor dl, torch::Tensor conf_indptr, torch::Tensor conf_base,
     torch::Tensor conf_cols, torch::Tensor rates, torch::Tensor bw_comp,
     torch::Tensor E_arr, torch::Tensor T_arr, long Ee, long iters,
-    double cap) {
+    double cap, c10::optional<torch::Tensor> node_vedge) {
     const int B = route_links.size(0), J = route_links.size(1);
     const int H = route_links.size(2);
     const int E = rates.size(1), C = bw_comp.size(1);
+    // with node_vedge (B,N), `vedge_dst` holds the destination NODES and the
+    // kernel looks their compute slots up itself
+    const long* nv = nullptr;
+    int N = 0;
+    if (node_vedge.has_value()) {
+        TORCH_CHECK(node_vedge->scalar_type() == torch::kInt64
+                    && node_vedge->dim() == 2 && node_vedge->size(0) == B
+                    && node_vedge->is_contiguous()
+                    && vedge_dst.is_contiguous(),
+                    "critic: node_vedge is a contiguous (B,N) int64");
+        nv = node_vedge->data_ptr<long>();
+        N = node_vedge->size(1);
+    }
     auto loss = torch::empty({B}, rates.options());
     const CriticPlan p = critic_plan(E, (int)Ee, (int)iters);
     TORCH_CHECK(p.fits, "graph too large even for the global-scratch critic");
@@ -425,7 +456,7 @@ std::vector<torch::Tensor> critic_hip(
     hipLaunchKernelGGL(critic_kernel, dim3(B), dim3(p.threads),
                        launch_lds_bytes(p, budget), stream.stream(),
                        route_links.data_ptr<int>(), nhop.data_ptr<int>(),
-                       vedge_dst.data_ptr<long>(), mask.data_ptr<bool>(),
+                       vedge_dst.data_ptr<long>(), nv, mask.data_ptr<bool>(),
                        rate.data_ptr<float>(), ul.data_ptr<float>(),
                        dl.data_ptr<float>(),
                        tables(conf_indptr, conf_base, conf_cols, rates,
@@ -433,7 +464,7 @@ std::vector<torch::Tensor> critic_hip(
                        grad_edge.data_ptr<float>(), loss.data_ptr<float>(),
                        g_hist.data_ptr<float>(), g_dunit.data_ptr<float>(),
                        g_dlam.data_ptr<float>(), p, (float)cap, budget,
-                       E, C, (int)Ee, J, H, (int)iters);
+                       E, C, (int)Ee, J, H, (int)iters, N);
     return {grad_edge, loss};
 }
 
@@ -476,7 +507,7 @@ torch::Tensor actor_head_bwd_launch(
     torch::Tensor E_arr, long iters, double cap) {
     const int B = lam_ext.size(0), Ee = lam_ext.size(1);
     const int E = rates.size(1), C = bw_comp.size(1);
-    auto dlam = torch::zeros_like(lam_ext);
+    auto dlam = torch::empty_like(lam_ext);    // the kernel writes all of it
     const ActorBwdPlan p = actor_bwd_plan(E, (int)iters);
     TORCH_CHECK(p.fits, "graph too large for LDS actor head bwd");
     auto stream = at::cuda::getCurrentCUDAStream();
@@ -515,16 +546,23 @@ torch::Tensor actor_head_bwd_hip(
 // walk_eval_kernel (episode.hip, stages 3/3b) sets `written` only at
 // (u,v)/(v,u) of a routed real link and at (d,d) of a destination, i.e.
 // inside the 2·E_b + N cells visited here, so the anchor mask is covered.
-// Returns (dλ (B,Ee), loss_mse 0-dim).
+// Returns (dλ (B,Ee), loss_mse 0-dim), and with `critic_loss` (the critic's
+// per-graph loss) a third 0-dim tensor, its sum.
 std::vector<torch::Tensor> actor_head_bwd_fused_hip(
     torch::Tensor grad_edge, torch::Tensor dm, torch::Tensor unit_mtx,
     torch::Tensor written, torch::Tensor lam_ext, torch::Tensor mu_hist,
     torch::Tensor conf_indptr, torch::Tensor conf_base,
     torch::Tensor conf_cols, torch::Tensor rates, torch::Tensor bw_comp,
     torch::Tensor edges, torch::Tensor node_vedge, torch::Tensor T_arr,
-    torch::Tensor E_arr, long iters, double cap) {
+    torch::Tensor E_arr, long iters, double cap,
+    c10::optional<torch::Tensor> critic_loss) {
     const int B = lam_ext.size(0), Ee = lam_ext.size(1);
     const int N = dm.size(1);
+    if (critic_loss.has_value())
+        TORCH_CHECK(critic_loss->scalar_type() == torch::kFloat32
+                    && critic_loss->numel() == B
+                    && critic_loss->is_contiguous(),
+                    "critic_loss is the critic's (B,) fp32 loss");
     TORCH_CHECK(grad_edge.is_contiguous() && dm.is_contiguous()
                 && unit_mtx.is_contiguous() && written.is_contiguous()
                 && lam_ext.is_contiguous(), "contiguous inputs expected");
@@ -541,10 +579,15 @@ std::vector<torch::Tensor> actor_head_bwd_fused_hip(
         N, lam_ext, mu_hist, conf_indptr, conf_base, conf_cols, rates,
         bw_comp, edges, node_vedge, T_arr, E_arr, iters, cap);
     auto loss_mse = torch::empty({}, lam_ext.options());
+    auto loss_fn = torch::empty({}, lam_ext.options());
     hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0,
                        at::cuda::getCurrentCUDAStream().stream(),
-                       mse_sq.data_ptr<float>(), mse_cnt.data_ptr<int>(), B,
-                       loss_mse.data_ptr<float>());
+                       mse_sq.data_ptr<float>(), mse_cnt.data_ptr<int>(),
+                       critic_loss.has_value()
+                           ? critic_loss->data_ptr<float>() : nullptr,
+                       B, loss_mse.data_ptr<float>(),
+                       loss_fn.data_ptr<float>());
+    if (critic_loss.has_value()) return {dlam, loss_mse, loss_fn};
     return {dlam, loss_mse};
 }
 

@@ -36,6 +36,11 @@ stack and with a 3-layer one (first, one middle, last layer — the kernels
 take L from ``W``): (t5 - t3) / 2 is one middle layer, the rest of t5 the two
 edge layers and the launch.  On a build without the switch it times the
 kernels as they are.
+
+``--config adam`` times the fused Adam launch alone on the benchmark's model
+(one workgroup per tensor against ``adam_force_single_block``), and
+``--config walk`` the walk_eval launch and ``eng._episode_eval`` around it,
+both at B=256 and B=1024.
 """
 import argparse
 import json
@@ -496,13 +501,95 @@ def bench_cheb(batches=(256, 1024), reps=200):
             print(json.dumps(row), flush=True)
 
 
+def _bench_engine(batch):
+    """The benchmark's own batch (BA-100, seed 100) and model."""
+    from multihop_offload_amd.engine import EpisodeEngine
+    from multihop_offload_amd.models.chebconv import ChebConvStack
+    from multihop_offload_amd.harness.train_batched import build_training_cases
+
+    cases = build_training_cases(100, batch, 16, 1000, 100, gtype="ba",
+                                 workers=8)
+    model = ChebConvStack(K=2, dtype=torch.float32, seed=100)
+    return EpisodeEngine(cases, model, device="cuda", dtype=torch.float32)
+
+
+def bench_adam(batches=(256, 1024), reps=200):
+    """``FusedAdam.step`` alone (one fused_adam launch) on the benchmark's
+    model, with the gradients one training episode of the benchmark's batch
+    leaves in ``flat_g``: the one-workgroup-per-tensor kernel against the
+    single-block one (``adam_force_single_block``).  The kernel sees the
+    batch only through the gradient values.  On a build without the switch it
+    times the kernel as it is."""
+    from multihop_offload_amd.ops import dispatch
+    from multihop_offload_amd.ops.functions import FusedAdam
+
+    ext = dispatch.require_hip()
+    has_switch = hasattr(ext, "adam_force_single_block")
+    modes = ["blocks", "single"] if has_switch else ["as_built"]
+    for batch in batches:
+        eng = _bench_engine(batch)
+        opt = FusedAdam(eng.model, lr=1e-4)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(0)
+        opt.zero_grad()
+        eng.gnn_episode(eng.sample_jobs(0.15, gen), explore=0.0, gen=gen,
+                        train=True)
+        row = {"config": "adam", "B": eng.B, "n_seg": int(opt.seg.shape[0]),
+               "n_param": int(opt.flat_p.numel())}
+        for mode in modes:
+            if has_switch:
+                ext.adam_force_single_block(mode == "single")
+            # scale 1: the gradient keeps its magnitude over the launches
+            row[mode + "_us"] = round(
+                timeit(lambda: opt.step(scale=1.0), reps, 20), 1)
+        if has_switch:
+            ext.adam_force_single_block(False)
+        print(json.dumps(row), flush=True)
+
+
+def bench_walk(batches=(256, 1024), reps=200):
+    """``eng._episode_eval`` (one walk_eval launch, its output allocations
+    and the overflow bookkeeping around it) and the bare ``ext.walk_eval``
+    call on the benchmark's batch, after the step's own forward, APSP and
+    decision."""
+    from multihop_offload_amd.ops import dispatch
+
+    ext = dispatch.require_hip()
+    for batch in batches:
+        eng = _bench_engine(batch)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(0)
+        jobs = eng.sample_jobs(0.15, gen)
+        with torch.no_grad():
+            dm, *_ = eng.actor_forward(jobs)
+        dm = dm.detach()
+        sp = eng.apsp(dm)
+        uds = torch.diagonal(dm, dim1=1, dim2=2)
+        dst, _ = eng.offload_decide(jobs, sp, uds)
+        args = (sp.contiguous(), jobs.sources, dst.contiguous(), jobs.mask,
+                jobs.rates.contiguous(), jobs.ul.contiguous(),
+                jobs.dl.contiguous(), eng.k_adj_indptr, eng.k_adj_idx,
+                eng.k_adj_link, eng.k_conf_indptr, eng.k_conf_base,
+                eng.k_conf_cols, eng.link_rates.contiguous(),
+                eng.proc_bws.contiguous(), eng.k_edges,
+                eng.T_arr.contiguous(), eng.k_E_arr, eng.k_N_arr,
+                min(eng.walk_cap, 64), eng.fp_iters)
+        row = {"config": "walk", "B": eng.B, "N": eng.N, "E": eng.E,
+               "J": eng.Jmax}
+        row["walk_eval_us"] = round(
+            timeit(lambda: ext.walk_eval(*args), reps, 20), 1)
+        row["episode_eval_us"] = round(
+            timeit(lambda: eng._episode_eval(jobs, dst, sp), reps, 20), 1)
+        print(json.dumps(row), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="both",
                     choices=["flagship", "er1000", "both", "timeslot",
                              "timeslot_stats", "timeslot_mwis",
                              "timeslot_mwis_stats", "fixedpoint", "apsp",
-                             "cheb"])
+                             "cheb", "adam", "walk"])
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--budgets", type=str, default="-1",
                     help="fixedpoint: staging budgets in bytes, comma-"
@@ -516,6 +603,10 @@ if __name__ == "__main__":
         bench_apsp(reps=max(args.reps, 200))
     if args.config == "cheb":
         bench_cheb(reps=max(args.reps, 200))
+    if args.config == "adam":
+        bench_adam(reps=max(args.reps, 200))
+    if args.config == "walk":
+        bench_walk(reps=max(args.reps, 200))
     if args.config == "timeslot":
         bench_timeslot(reps=args.reps)
     if args.config == "timeslot_stats":
