@@ -782,10 +782,15 @@ class EpisodeEngine:
         costs = torch.cat([server_costs, local[..., None]], dim=2)  # (B,J,S+1)
 
         if prob:
-            logits = costs.clamp(max=1e30)
+            # the maximum runs over the finite costs only, as in the kernel:
+            # a padded server slot or an unreachable server (inf) would
+            # otherwise clamp to 1e30 and leave every real choice at weight 0
+            fin = torch.isfinite(costs)
+            logits = torch.where(fin, costs.clamp(max=1e30),
+                                 torch.full_like(costs, float("-inf")))
             logits = logits - logits.amax(dim=2, keepdim=True)
             p = torch.exp(logits)
-            p = torch.where(torch.isfinite(costs), p, torch.zeros_like(p))
+            p = torch.where(fin, p, torch.zeros_like(p))
             choice = torch.multinomial(
                 p.reshape(B * J, S + 1), 1, generator=gen).reshape(B, J)
         else:

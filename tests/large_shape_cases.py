@@ -123,7 +123,9 @@ def cheb_stack(A, x, W, bias, dlam, dtype):
     """The Chebyshev recurrence of models/chebconv.py, dense per graph, in
     ``dtype``; dW (B,L,K,32,32) and db (B,L,32) per graph from autograd of
     sum(lam·dlam).  Returns lam, the (B,L+1,Ee,32) activations, the
-    (B,L,Ee,32) pre-activations and their gradients delta, dW, db."""
+    (B,L,K-1,Ee,32) Chebyshev terms T_1..T_{K-1} of every layer's input
+    (None at K = 1), the (B,L,Ee,32) pre-activations and their gradients
+    delta, dW, db."""
     B, Ee = x.shape[:2]
     K = W.shape[1]
     A = A.to(dtype)
@@ -131,15 +133,18 @@ def cheb_stack(A, x, W, bias, dlam, dtype):
     bd = bias.to(dtype).unsqueeze(0).repeat(B, 1, 1).requires_grad_()
     h = torch.zeros(B, Ee, F, dtype=dtype)
     h[:, :, :FIN] = x.to(dtype)
-    acts, pres = [h], []
+    acts, pres, tks = [h], [], []
     for l in range(L):
         out = h @ Wd[:, l, 0]
         if K > 1:
             t_prev, t_cur = h, A @ h
+            terms = [t_cur]
             out = out + t_cur @ Wd[:, l, 1]
             for k in range(2, K):
                 t_prev, t_cur = t_cur, 2.0 * (A @ t_cur) - t_prev
+                terms.append(t_cur)
                 out = out + t_cur @ Wd[:, l, k]
+            tks.append(torch.stack(terms, 1).detach())
         out = out + bd[:, l].unsqueeze(1)
         out.retain_grad()
         pres.append(out)
@@ -149,6 +154,7 @@ def cheb_stack(A, x, W, bias, dlam, dtype):
     lam = h[:, :, 0]
     (lam * dlam.to(dtype)).sum().backward()
     return dict(lam=lam.detach(), acts=torch.stack(acts, 1).detach(),
+                tks=torch.stack(tks, 1) if K > 1 else None,
                 pres=torch.stack(pres, 1).detach(),
                 delta=torch.stack([p.grad for p in pres], 1),
                 dW=Wd.grad, db=bd.grad)
@@ -271,11 +277,17 @@ def _try_cheb_case(Ee, K, padded, tile, seed):
     ref_err = {k: float(grad_errors(ref32[k], want[k]).max())
                for k in ("dW", "db")}
     tol = {k: min(8.0 * max(v, 2.0 ** -24), 5e-3) for k, v in ref_err.items()}
-    return dict(Ee=Ee, K=K, B=B, padded=padded, tile=tile, seed=seed, A=A,
+    case = dict(Ee=Ee, K=K, B=B, padded=padded, tile=tile, seed=seed, A=A,
                 indptr=indptr, base=base, cols=cols, max_nnz=max_nnz, x=x,
                 dlam=dlam, W=W, bias=bias, want=want,
                 dmax=float(A.sum(2).max()), fwd_err32=fwd_err32, kink=kink,
-                ref_err=ref_err, tol=tol)
+                ref_err=ref_err, tol=tol, tks_err32=None)
+    if K > 1:
+        # the fp32 reference's Chebyshev terms, as a share of the forward
+        # bound (the terms grow like the spectrum of A to the power k)
+        err = (ref32["tks"].double() - want["tks"]).abs()
+        case["tks_err32"] = float((err / fwd_bound(case, want["tks"])).max())
+    return case
 
 
 @functools.lru_cache(maxsize=None)
@@ -304,6 +316,13 @@ def fwd_bound(case, want):
 ROW_TILED = [(Ee, K) for Ee in (129, 192, 385) for K in (1, 2)]
 LDS_TOP = [(377, 2), (384, 2), (400, 1), (368, 3)]
 UNSTAGED = [(85, 2), (85, 3)]          # B=2, unpadded
+# generic-K kernels past K = 3 (Ee, K, padded): the backward's reverse
+# recurrence runs K - 2 times, so an even and an odd K end on opposite
+# buffers; three row tiles with the empty band; the largest Ee the
+# LDS-resident family accepts at K = 4 and K = 5
+GENERIC_K = [(85, 4, False), (85, 5, False), (129, 4, True), (129, 5, True),
+             (368, 4, True), (352, 5, False), (61, 6, False)]
+GENERIC_K_TOP = [(368, 4), (352, 5)]
 # a max_nnz whose CSR alone exceeds the LDS: every plan reads the CSR from
 # global memory.  The kernels copy or read only the true indptr[Ee] entries.
 INFLATED_NNZ = 1 << 16

@@ -9,7 +9,9 @@ checked on the CPU by tests/test_large_shape_inputs.py):
 * the LDS-resident families (chebconv.hip) at the largest shapes they
   accept, where the backward no longer stages the support CSR in LDS;
 * every LDS-resident kernel with the CSR read from global memory, against
-  its own staged run.
+  its own staged run;
+* the generic-K kernels at K = 4, 5 and 6, where the backward's reverse
+  recurrence runs more than once (forward, saved terms and gradients).
 
 Padded batches: graph 1 has an empty band of rows across a tile boundary and
 an empty tail; every comparison covers those rows.
@@ -192,6 +194,42 @@ def test_lds_resident_families_at_their_largest_shapes(Ee, K):
         tag = f"{family} Ee={Ee} K={K}"
         _check_forward(tag, case, lam, acts, slots)
         _check_grads(tag, case, dW, db)
+
+
+@needs_gpu
+@pytest.mark.parametrize("Ee,K,padded", lc.GENERIC_K)
+def test_generic_k_beyond_three(Ee, K, padded):
+    """cheb_kn_fwd / cheb_kn_bwd at K = 4, 5 and 6, called directly.  From
+    K = 4 on the backward's reverse recurrence runs more than once, so the
+    swap of its two buffers and the weight slot of each step matter, and an
+    even and an odd K end on opposite buffers; the K = 3 tests cannot see
+    either.  lam, every activation slot, the K - 1 saved Chebyshev terms of
+    every layer, dW and db against the fp64 oracle; the padded cases have
+    three row tiles and the empty band, (368, 4) and (352, 5) are the
+    largest shapes ``cheb_fits_lds`` accepts and run their backward with
+    the support CSR in global memory, the others stage it."""
+    ext = _ext()
+    case = lc.cheb_case(Ee, K, padded)
+    nnz = case["max_nnz"]
+    top = (Ee, K) in lc.GENERIC_K_TOP
+    if top:
+        assert ext.cheb_fits_lds(Ee, K) and not ext.cheb_fits_lds(Ee + 1, K)
+    plan = _plan(Ee, K, nnz)
+    assert plan["kn_fwd"]["fits"] and plan["kn_bwd"]["fits"]
+    assert plan["kn_bwd"]["stage_csr"] == (0 if top else 1)
+    lam, acts, tks, dW, db, slots = _run_lds(case, nnz, "cheb_kn")
+    tag = f"cheb_kn Ee={Ee} K={K}"
+    _check_forward(tag, case, lam, acts, slots)
+    want = case["want"]["tks"]
+    assert tuple(tks.shape) == (case["B"], L, K - 1, Ee, lc.F)
+    err = (tks.double().cpu() - want).abs()
+    bound = lc.fwd_bound(case, want)
+    print(f"{tag} tks: largest err / bound {float((err / bound).max()):.3f} "
+          f"(fp32 reference {case['tks_err32']:.3f}), largest term "
+          f"{float(want.abs().max()):.3e}")
+    assert bool(torch.isfinite(tks).all()), tag
+    assert bool((err <= bound).all()), tag
+    _check_grads(tag, case, dW, db)
 
 
 @needs_gpu

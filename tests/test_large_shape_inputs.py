@@ -13,7 +13,8 @@ from tests import large_shape_cases as lc
 
 CHEB = ([(Ee, K, True, None) for Ee, K in lc.ROW_TILED + lc.LDS_TOP]
         + [(Ee, K, False, None) for Ee, K in lc.UNSTAGED]
-        + [(Ee, K, False, tile) for Ee, K, tile in lc.ONE_TILE])
+        + [(Ee, K, False, tile) for Ee, K, tile in lc.ONE_TILE]
+        + [(Ee, K, padded, None) for Ee, K, padded in lc.GENERIC_K])
 
 
 # ---------------------------------------------------------- Floyd–Warshall
@@ -131,6 +132,18 @@ def test_cheb_inputs_are_conditioned(Ee, K, padded, tile):
         assert c["tol"][k] == min(8.0 * max(c["ref_err"][k], 2.0 ** -24),
                                   5e-3)
         assert c["ref_err"][k] < 1e-4       # the recipe is well conditioned
+    if K > 1:
+        # the oracle's saved terms are the recurrence on its own activations
+        tks, h = want["tks"], want["acts"][:, :lc.L]
+        assert tuple(tks.shape) == (B, lc.L, K - 1, Ee, lc.F)
+        terms = [h, A[:, None] @ h]
+        for k in range(2, K):
+            terms.append(2.0 * (A[:, None] @ terms[-1]) - terms[-2])
+        assert torch.allclose(tks, torch.stack(terms[1:], 2), rtol=0,
+                              atol=1e-12 * float(tks.abs().max()))
+        print(f"largest term {float(tks.abs().max()):.3e}, fp32-reference "
+              f"error of the terms {c['tks_err32']:.3f} of the forward bound")
+        assert c["tks_err32"] < 1.0
 
     if padded:
         empty = lc.empty_rows(Ee, 1, True)
@@ -190,6 +203,23 @@ def test_cheb_shapes_reach_the_documented_paths():
     for Ee, K in lc.LDS_TOP:
         p = lc.lds_plans(Ee, K, lc.cheb_case(Ee, K)["max_nnz"])
         assert p["kn_bwd" if K > 2 else "bwd"]["stage_csr"] == 0, (Ee, K)
+    # generic K past 3: the reverse recurrence of the backward runs K - 2
+    # times, twice or more and on both parities; the two top shapes are the
+    # largest of their K and alone run the backward unstaged
+    assert sorted({K for _, K, _ in lc.GENERIC_K}) == [4, 5, 6]
+    assert all(K - 2 >= 2 for _, K, _ in lc.GENERIC_K)
+    for K, top in ((4, 368), (5, 352)):
+        assert lc.fits_lds(top, K) and not lc.fits_lds(top + 1, K)
+        assert (top, K) in lc.GENERIC_K_TOP
+    assert {(Ee, K) for Ee, K, _ in lc.GENERIC_K} >= set(lc.GENERIC_K_TOP)
+    for Ee, K, padded in lc.GENERIC_K:
+        assert lc.fits_lds(Ee, K)
+        p = lc.lds_plans(Ee, K, lc.cheb_case(Ee, K, padded)["max_nnz"])
+        assert p["kn_fwd"]["fits"] and p["kn_bwd"]["fits"]
+        assert p["kn_bwd"]["stage_csr"] == \
+            (0 if (Ee, K) in lc.GENERIC_K_TOP else 1), (Ee, K)
+    assert [(Ee + 63) // 64 for Ee, _, padded in lc.GENERIC_K if padded] == \
+        [3, 3, 6]
     # the small shape stages everything at its own max_nnz and nothing at
     # the inflated one the unstaged test passes
     for Ee, K in lc.UNSTAGED:
